@@ -18,7 +18,11 @@ max_disp 192 -> 216 as the reference rounds it, demo.py:153):
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     python bench.py --config 5 --gpus 4                   (training share: SpaMat fwd+bwd + gradient all-reduce)
 
-Rank 0 prints ONE JSON line (see README / DESIGN.md for the fields).
+Rank 0 prints ONE JSON line (see README / DESIGN.md for the fields).  A plain run sets up, warms up, times the K steps and
+prints the headline figure only (value, ms_per_step, ...).  --full adds everything else the line can carry: repeat blocks,
+rooflines of the dominant kernels, mask-density sweeps, the training share, the whole graph, the fp32 GEMM variant, the CPU
+baselines and, with collectives, their own latency and check; the --no-* switches leave single parts of that out.
+--dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy (float32, see dump_outputs).
 """
 import argparse
 import json
@@ -46,6 +50,10 @@ CONFIGS = {
 }
 N_PARAMS = 13_190_000        # parameters of the shipped base_channels=8 network: 52.7 MB of fp32 gradients
 CONFIG_NAME, PAD_H, PAD_W, MAX_DISP, DEFAULT_B = CONFIGS[2]
+DTYPE_BF16X3 = "f32 (bf16x3 on the bf16 matrix pipe)"
+# --dump-outputs: an output of more elements than this is written as a fixed sample of that many (4 MB of float32 per
+# file; with at most 15 outputs per step that keeps a dump under 64 MB)
+DUMP_MAX_ELEMS = 1 << 20
 
 
 _JSON_OUT = None       # the process's real stdout when a process group is up (see main)
@@ -121,6 +129,19 @@ class HotPath:
         self.ev = None
         self.gstream = None                             # the stream the all-gather is issued from (round 4)
         self.overlap = True                             # --no-overlap: everything in order on one stream
+        self.pred0 = None                               # stage 0's disparity of the latest step
+
+    def outputs(self):
+        """What the latest step computed, by name (call after drain()): stage 0's disparity, the four SpaMat/SpaVar
+        outputs of stages 1-3 and, with collectives, the gathered stage-3 disparity maps of all ranks."""
+        par = (self.k - 1) & 1 if self.coll else 0
+        out = {"stage0_disparity": self.pred0}
+        for s, bufs in ((1, self.outs[0]), (2, self.outs[1]), (3, self.outs3[par])):
+            for name, t in zip(("disparity", "variance", "sum_similarities", "max_cost"), bufs):
+                out["stage%d_%s" % (s, name)] = t
+        if self.coll:
+            out["gathered_stage3_disparity"] = self.gbuf[par]
+        return out
 
     def drain(self):
         """Wait for the all-gathers still in flight (end of a timed region)."""
@@ -198,7 +219,33 @@ class HotPath:
                                                                      out=self.gbuf[par], async_op=True)
             self.gbuf[par] = disp
             self.k += 1
+        self.pred0 = pred0
         return pred0, disp
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: DIR/<name>.npy, float32, one file per output of the timed path's last step.  An output of more than
+    DUMP_MAX_ELEMS elements is written flattened, as the elements at a fixed set of flat indices (a seeded random sample,
+    sorted: the same indices in every run for the same shape), so that two builds can be compared output for output."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        a = t.detach().float()
+        if a.numel() > DUMP_MAX_ELEMS:
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_MAX_ELEMS].sort().values
+            a = a.reshape(-1)[idx.to(a.device)]
+        a = a.cpu().numpy()
+        total += a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    assert total <= 64 << 20, "--dump-outputs wrote %d bytes" % total
+
+
+def stage0_bf16x3(C0, D0):
+    """True where stage 0's Winograd GEMMs run fp32 operands as three bf16 terms on the bf16 matrix pipe (the default at
+    Ci = 216); False for the fp32 MFMA GEMM (DECNET_WINO_GEMM=fp32) and the direct convolution."""
+    from decnet_amd.stage0 import conv_algo, WINO_VARIANT
+    return conv_algo(D0) in WINO_VARIANT and C0 == 216 and os.environ.get("DECNET_WINO_GEMM", "") in ("", "bf16x3")
 
 
 def time_kernel(fn, iters, warm=10):
@@ -371,8 +418,8 @@ def live_traffic(config):
         for counter in ("FETCH_SIZE", "WRITE_SIZE"):
             d = os.path.join(tmp, counter)
             cmd = ["rocprofv3", "--pmc", counter, "--output-format", "csv", "-d", d, "-o", "p", "--",
-                   sys.executable, os.path.abspath(__file__), "--config", str(config), "--steps", "3", "--warmup", "1",
-                   "--no-cpu-baseline", "--no-e2e", "--no-train", "--no-density-sweep", "--no-alt", "--no-valu-floor",
+                   sys.executable, os.path.abspath(__file__), "--full", "--config", str(config), "--steps", "3",
+                   "--warmup", "1", "--no-cpu-baseline", "--no-e2e", "--no-train", "--no-density-sweep", "--no-alt", "--no-valu-floor",
                    "--no-live-traffic", "--no-blocks"]
             env = dict(os.environ, TMPDIR="/tmp")
             for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
@@ -415,8 +462,8 @@ def alt_gemm_leg():
     default, beside this round's bf16x3 default."""
     import subprocess
     env = dict(os.environ, DECNET_WINO_GEMM="fp32")
-    cmd = [sys.executable, os.path.abspath(__file__), "--steps", "50", "--warmup", "8", "--no-cpu-baseline", "--no-train",
-           "--no-density-sweep", "--no-e2e", "--no-alt", "--no-live-traffic", "--no-valu-floor", "--no-blocks"]
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--steps", "50", "--warmup", "8", "--no-cpu-baseline",
+           "--no-train", "--no-density-sweep", "--no-e2e", "--no-alt", "--no-live-traffic", "--no-valu-floor", "--no-blocks"]
     try:
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
         d = json.loads(r.stdout.strip().splitlines()[-1])
@@ -868,6 +915,16 @@ class TrainShare:
     def drain(self):
         pass
 
+    def outputs(self):
+        """What the latest step computed at stages 1-3, by name: the SpaMat forward's outputs and both gradients."""
+        out = {}
+        for s in (1, 2, 3):
+            b = self.buf[s]
+            for name, k in (("disparity", "o"), ("sum_similarities", "ss"), ("max_cost", "mc"), ("grad_ref", "gl"),
+                            ("grad_tar", "gr")):
+                out["stage%d_%s" % (s, name)] = b[k]
+        return out
+
 
 def timed_region(step, drain, warmup, steps, world, dev):
     """W untimed steps, then exactly K steps between barrier + synchronize on both sides; MAX over ranks."""
@@ -954,53 +1011,78 @@ def main_train(args, B, dev, world, rank):
     ts = TrainShare(B, dev, args.mask_density, world)
     with torch.no_grad():
         elapsed = timed_region(ts.step, ts.drain, args.warmup, args.steps, world, dev)
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, ts.outputs())
         t_ar = None
-        if ts.coll:                                      # the gradient all-reduce alone, not overlapped: a
+        if ts.coll and args.full:                        # the gradient all-reduce alone, not overlapped: a
             def ar():                                    # collective, so EVERY rank runs it (outside the timed region)
                 for i in range(len(ts.grads)):
                     ts.grads.reduce_async(i)
                 ts.grads.wait()
             t_ar = time_kernel(ar, 10, warm=3)
         if rank == 0:
-            ms_step = 1e3 * elapsed / args.steps
-            C, H, W, D = STAGES[3]
-            (L, R), (rm, tm), b = ts.feats[3], ts.masks[3], ts.buf[3]
-            tb = time_kernel(lambda: ts.ops.spamat_backward(L, R, rm, tm, b["o"], b["ss"], b["mc"], b["go"], b["gl"],
-                                                            b["gr"], D), 30)
-            tf = time_kernel(lambda: ts.ops.spamat_forward(L, R, rm, tm, b["o"], b["ss"], b["mc"], D), 30)
-            nb = 4.0 * B * H * W * (4 * C + 6)
-            traffic = {}
-            try:
-                with open(os.path.join(ROOT, "profiles", "traffic.json")) as f:
-                    traffic = json.load(f)
-            except (OSError, ValueError):
-                pass
             out = {
                 "metric": "stereo pairs/sec, BASELINE config 5 share (SpaMat forward+backward, stages 1-3, + "
                           "all-reduce of a SYNTHETIC 52.7 MB gradient buffer: the 2-D trunk's backward is outside the path)",
                 "value": world * B * args.steps / elapsed, "unit": "pairs/s", "n_gpus": world, "steps": args.steps,
-                "warmup": args.warmup, "ms_per_step": ms_step, "higher_is_better": True, "scaling": "weak",
-                "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+                "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True,
+                "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
                 "config": {"workload": "BASELINE %s: %d pairs per GPU, feature maps of the 4-stage/scale-3 net; the "
                                        "gradient buffer is synthetic (the 2-D trunk's backward is outside the path)"
                                        % (CONFIG_NAME, B),
                            "pairs_per_gpu": B, "mask_density": args.mask_density, "grad_bytes": 4 * N_PARAMS,
                            "grad_buckets": len(ts.grads),
                            "parallelism": "dp%d (pairs sharded, bucketed all_reduce of gradients)" % world},
-                "roofline": {"bound": "hbm", "achieved": nb / tb / 1e6, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                             "frac": nb / tb / 1e6 / HBM_PEAK_GBS,
-                             "traffic": traffic.get("spamat_bwd_stage3", {}).get("total_bytes"),
-                             "kernel": "spamat backward (ref + tar gradient launches), stage 3", "ms": tb,
-                             "bytes_per_launch": nb, "fwd_ms": tf},
-                "allreduce_alone_ms": t_ar,
             }
-            if ts.coll:
-                out["collective"] = {"backend": torch.distributed.get_backend(), "world": world,
-                                     "forced_at_world_1": world == 1, "allreduce_4_buckets_alone_ms": t_ar}
+            if args.full:
+                C, H, W, D = STAGES[3]
+                (L, R), (rm, tm), b = ts.feats[3], ts.masks[3], ts.buf[3]
+                tb = time_kernel(lambda: ts.ops.spamat_backward(L, R, rm, tm, b["o"], b["ss"], b["mc"], b["go"],
+                                                                b["gl"], b["gr"], D), 30)
+                tf = time_kernel(lambda: ts.ops.spamat_forward(L, R, rm, tm, b["o"], b["ss"], b["mc"], D), 30)
+                nb = 4.0 * B * H * W * (4 * C + 6)
+                traffic = {}
+                try:
+                    with open(os.path.join(ROOT, "profiles", "traffic.json")) as f:
+                        traffic = json.load(f)
+                except (OSError, ValueError):
+                    pass
+                out["roofline"] = {"bound": "hbm", "achieved": nb / tb / 1e6, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                   "frac": nb / tb / 1e6 / HBM_PEAK_GBS,
+                                   "traffic": traffic.get("spamat_bwd_stage3", {}).get("total_bytes"),
+                                   "kernel": "spamat backward (ref + tar gradient launches), stage 3", "ms": tb,
+                                   "bytes_per_launch": nb, "fwd_ms": tf}
+                out["allreduce_alone_ms"] = t_ar
+                if ts.coll:
+                    out["collective"] = {"backend": torch.distributed.get_backend(), "world": world,
+                                         "forced_at_world_1": world == 1, "allreduce_4_buckets_alone_ms": t_ar}
             print(json.dumps(out), file=_JSON_OUT or sys.stdout, flush=True)
+    close_process_group()
+
+
+def close_process_group():
     if torch.distributed.is_initialized():
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
+
+
+def hot_path_line(args, world, B, elapsed):
+    """The headline fields of configs 2-4: every run prints them, --full adds its objects to them."""
+    C0, _, _, D0 = STAGES[0]
+    return {
+        "metric": ("stereo pairs/sec at 960x540x192disp" if args.config == 2 else
+                   "stereo pairs/sec, BASELINE config %d shapes" % args.config) +
+                  " (hot path: stage-0 dense + SpaMat/SpaVar stages 1-3)",
+        "value": world * B * args.steps / elapsed, "unit": "pairs/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None,
+        "dtype": DTYPE_BF16X3 if stage0_bf16x3(C0, D0) else "f32", "data": "synthetic",
+        "config": {"workload": "BASELINE %s: batch=%d synthetic pairs per GPU, feature maps of the "
+                               "4-stage/scale-3 net, random-init CostRegNetNoDown(216)" % (CONFIG_NAME, B),
+                   "pairs_per_gpu": B, "mask_density": args.mask_density,
+                   "parallelism": "dp%d (pairs sharded, all_gather of disparity maps)" % world},
+        "preconditioning_steps": args.precondition_steps,
+    }
 
 
 def main():
@@ -1038,7 +1120,8 @@ def main():
     ap.add_argument("--force-collective", action="store_true",
                     help="initialise RCCL (backend nccl) and run the per-step collectives (all-gather of the disparity "
                          "maps; config 5: the bucketed gradient all-reduce) even with ONE rank: the N > 1 code path on a "
-                         "one-GPU box.  Adds a 'collective' object with the collective's latency and an equality check")
+                         "one-GPU box.  With --full, adds a 'collective' object with the collective's latency and an "
+                         "equality check")
     ap.add_argument("--no-e2e-table", action="store_true",
                     help="skip e2e.roofline: the per-kernel-family table of one forward (a child process under "
                          "rocprofv3 --kernel-trace)")
@@ -1051,6 +1134,13 @@ def main():
     ap.add_argument("--no-e2e", action="store_true",
                     help="skip the extra 'e2e' object: the whole inference graph (decnet_amd.model: the 2-D "
                          "trunk around the hot path) timed on the same batch, eager and as a HIP-graph replay")
+    ap.add_argument("--full", action="store_true",
+                    help="measure more than the headline figure: value_blocks, rooflines, density sweeps, train, e2e, the "
+                         "fp32 GEMM variant, CPU baselines, the collective's own latency (the --no-* switches above leave "
+                         "parts of it out).  Without it the run times the K steps and prints the headline fields only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32; an output "
+                         "of more than %d elements as a fixed seeded sample of them)" % DUMP_MAX_ELEMS)
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1111,6 +1201,12 @@ def main():
         hp.drain()
         torch.cuda.synchronize()
         elapsed = timed_region(hp.step, hp.drain, args.warmup, args.steps, world, dev)
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, hp.outputs())
+        if not args.full:
+            if rank == 0:
+                print(json.dumps(hot_path_line(args, world, B, elapsed)), file=_JSON_OUT or sys.stdout, flush=True)
+            return close_process_group()
         blocks = None if args.no_blocks else value_blocks(hp.step, hp.drain, args.steps, world, dev, world * B)
         smi = smi_under_load(hp.step, hp.drain) if (rank == 0 and world == 1 and not args.no_blocks) else None
         # per-stage breakdown from a few extra steps with events around stage 0 and stage 3 (an event
@@ -1131,8 +1227,6 @@ def main():
                 traffic = json.load(f)
         except (OSError, ValueError):
             pass
-        ms_step = 1e3 * elapsed / args.steps
-        pairs = world * B * args.steps
         # --- dominant kernel, timed live with events on the launch stream -------------------
         C0, H0, W0, D0 = STAGES[0]
         M = B * D0 * H0 * W0
@@ -1179,7 +1273,7 @@ def main():
                 conv_ms = time_kernel(lambda: L.decnet_conv3d_wino_gemm(
                     V.data_ptr(), p0["u"].data_ptr(), Mw.data_ptr(), nt, C0, C0, var, st), 60)
                 kern_flop = 2.0 * npts * nt * C0 * C0
-                bf16x3 = C0 == 216 and os.environ.get("DECNET_WINO_GEMM", "") in ("", "bf16x3")
+                bf16x3 = stage0_bf16x3(C0, D0)
                 if bf16x3:
                     gemm_mult, gemm_peak = 6.0, MFMA_BF16_PEAK_TF
                     gemm_arith = "fp32 operands as three bf16 terms (round to nearest), six products on " \
@@ -1269,18 +1363,8 @@ def main():
         else:
             roof_head = dict(bound="mfma", achieved=roof_mfma["achieved"], peak=roof_mfma["peak"], unit=roof_mfma["unit"],
                              frac=roof_mfma["frac"], mfma=roof_mfma, hbm=roof_hbm)
-        out = {
-            "metric": ("stereo pairs/sec at 960x540x192disp" if args.config == 2 else
-                       "stereo pairs/sec, BASELINE config %d shapes" % args.config) +
-                      " (hot path: stage-0 dense + SpaMat/SpaVar stages 1-3)",
-            "value": pairs / elapsed, "unit": "pairs/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": ms_step, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32 (bf16x3 on the bf16 matrix pipe)" if gemm_mult > 1 else "f32", "data": "synthetic",
-            "config": {"workload": "BASELINE %s: batch=%d synthetic pairs per GPU, feature maps of the "
-                                   "4-stage/scale-3 net, random-init CostRegNetNoDown(216)" % (CONFIG_NAME, B),
-                       "pairs_per_gpu": B, "mask_density": args.mask_density,
-                       "parallelism": "dp%d (pairs sharded, all_gather of disparity maps)" % world},
+        out = hot_path_line(args, world, B, elapsed)
+        out.update({
             # bf16x3 (default at Ci = 216): every fp32 product of the GEMM is executed as six bf16 products on
             # v_mfma_f32_16x16x32_bf16, so the kernel is priced with its EXECUTED flops (6 x the algorithmic ones)
             # against the dense bf16 peak; fp32_equivalent_tflops = algorithmic flops / time (157.3 would be the fp32 peak)
@@ -1315,8 +1399,7 @@ def main():
                                          "candidates x ~12 VALU-op equivalents + 8 MFMA MACs each cap it near 0.2 "
                                          "of 8 TB/s (DESIGN.md section 4); the HBM-shaped regime is the sparse one "
                                          "in roofline_costvol_sparse"},
-        }
-        out["preconditioning_steps"] = args.precondition_steps
+        })
         if blocks:
             out["value_blocks"] = blocks
         if smi:
@@ -1394,9 +1477,7 @@ def main():
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(budget_s=args.cpu_budget)
         print(json.dumps(out), file=_JSON_OUT or sys.stdout, flush=True)
-    if torch.distributed.is_initialized():
-        torch.distributed.barrier()
-        torch.distributed.destroy_process_group()
+    close_process_group()
 
 
 if __name__ == "__main__":

@@ -70,3 +70,21 @@ def test_unit_kinds_resolve_to_their_own_family():
         assert pre in fams, (kind, pre)
         assert next(p for p in fams if p in pre + "<8>") == pre, (kind, pre)
     assert next(p for p in fams if p in "void (anonymous namespace)::deconv2d_k3s3<8>(float const*") == "deconv2d_k3s3"
+
+
+def test_dump_outputs_writes_float32_and_fixed_samples(tmp_path):
+    """bench.dump_outputs (--dump-outputs): small outputs whole and in their shape, large ones as the same seeded sample
+    of DUMP_MAX_ELEMS elements in every run, all float32."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    big = torch.arange(3 * bench.DUMP_MAX_ELEMS, dtype=torch.float64)
+    small = torch.ones(3, 4, dtype=torch.float16)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"big": big, "small": small})
+    a, b = (np.load(tmp_path / d / "big.npy") for d in ("a", "b"))
+    assert a.dtype == np.float32 and a.shape == (bench.DUMP_MAX_ELEMS,) and np.array_equal(a, b)
+    assert np.all(np.diff(a) > 0) and a.min() >= 0 and a.max() < 3 * bench.DUMP_MAX_ELEMS   # distinct elements of `big`
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and s.shape == (3, 4) and np.all(s == 1)

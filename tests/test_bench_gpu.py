@@ -1,5 +1,5 @@
-"""bench.py contract: one JSON line with the driver's keys, the roofline object of the dominant kernel and
-(at N = 1) the cpu_baseline object.  Short run; the numbers themselves are not asserted."""
+"""bench.py contract: one JSON line with the driver's keys; with --full also the roofline object of the dominant kernel
+and (at N = 1) the cpu_baseline object.  Short runs; the numbers themselves are not asserted."""
 import json
 import os
 import subprocess
@@ -11,10 +11,10 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(*flags, live_traffic=False):
+def _run(*flags, live_traffic=False, full=True):
     # (the live PMC count of roofline.traffic is two more child processes under rocprofv3: its own test below)
-    if not live_traffic:
-        flags = flags + ("--no-live-traffic",)
+    if full:
+        flags = ("--full",) + flags + (() if live_traffic else ("--no-live-traffic",))
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", *flags],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -68,6 +68,51 @@ def test_bench_line_contract():
     cfs = d["stage0_cost_funcs"]                       # the stage-0 branch with each --cost_func of the reference
     assert "error" not in cfs, cfs
     assert 0 < cfs["cor_ms"] and 0.7 < cfs["ssd_ms"] / cfs["cor_ms"] < 1.5 and 0.7 < cfs["cat_ms"] / cfs["cor_ms"] < 1.5
+
+
+def test_plain_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """Without --full the line holds the headline fields only, and --dump-outputs writes what the timed path computed in
+    its last step: the stage-1 outputs and stage 0's disparity equal the library's own results on bench.py's seeded
+    inputs (the rank-0 seed of HotPath), the stage-3 planes are fixed samples, and the whole dump stays under 64 MB."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    import decnet_amd
+    out = tmp_path / "dump"
+    d = _run("--dump-outputs", str(out), full=False)
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype",
+              "config"):
+        assert k in d, k
+    for k in ("roofline", "roofline_costvol", "value_blocks", "smi_under_load", "cpu_baseline", "train", "e2e",
+              "alt_wino_gemm_fp32", "stage0_cost_funcs"):
+        assert k not in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "pairs/s" and d["higher_is_better"] is True
+    assert abs(d["value"] - 8 * 3 / (d["ms_per_step"] * 3e-3)) < 1e-6 * d["value"]
+    assert d["dtype"] == bench.DTYPE_BF16X3
+    names = {"stage0_disparity"} | {"stage%d_%s" % (s, n) for s in (1, 2, 3)
+                                    for n in ("disparity", "variance", "sum_similarities", "max_cost")}
+    files = {p.stem: np.load(p) for p in out.glob("*.npy")}
+    assert set(files) == names
+    assert all(a.dtype == np.float32 for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    assert files["stage3_disparity"].shape == (bench.DUMP_MAX_ELEMS,)
+    dev = torch.device("cuda:0")
+    feats, masks = bench.make_inputs(8, dev, 1.0, seed=1000)
+    (L, R), (rm, tm) = feats[1], masks[1]
+    with torch.no_grad():
+        got = decnet_amd.spamatvar_forward(L, R, rm, tm, bench.STAGES[1][3])
+        for n, t in zip(("disparity", "variance", "sum_similarities", "max_cost"), got):
+            assert np.allclose(files["stage1_" + n], t.cpu().numpy(), rtol=1e-6, atol=1e-6), n
+        L0, R0 = feats[0]
+        pred = decnet_amd.Stage0(bench.make_regularizer(bench.STAGES[0][0], dev))(L0, R0, bench.STAGES[0][3])
+    assert np.allclose(files["stage0_disparity"], pred.cpu().numpy(), rtol=0, atol=1e-5)
+    # config 5: the SpaMat forward's outputs and both gradients of stages 1-3
+    out5 = tmp_path / "dump5"
+    d5 = _run("--config", "5", "--dump-outputs", str(out5), full=False)
+    assert "roofline" not in d5 and d5["steps"] == 3 and d5["value"] > 0
+    files = {p.stem: np.load(p) for p in out5.glob("*.npy")}
+    assert len(files) == 15 and sum(a.nbytes for a in files.values()) <= 64 << 20
 
 
 def test_costvol_density_map_and_e2e_objects():
@@ -182,9 +227,9 @@ def test_bench_collectives_run_through_rccl_in_a_world_of_one():
         port = sk.getsockname()[1]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     base = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
-            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5",
-            "--warmup", "2", "--force-collective", "--no-e2e", "--no-train", "--no-density-sweep", "--no-cpu-baseline",
-            "--no-alt"]
+            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1",
+            "--steps", "5", "--warmup", "2", "--force-collective", "--no-e2e", "--no-train", "--no-density-sweep",
+            "--no-cpu-baseline", "--no-alt"]
     for extra in ([], ["--config", "5"]):
         r = subprocess.run(base + extra, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
         assert r.returncode == 0, r.stderr[-2000:]

@@ -10,7 +10,7 @@ O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 # --no-alt / --no-valu-floor: no child processes under the profiler (they would inherit it and write their own stats)
-BENCH="python3 $R/bench.py --no-cpu-baseline --no-e2e --no-train --no-density-sweep --no-alt --no-valu-floor --no-live-traffic --no-blocks"
+BENCH="python3 $R/bench.py --full --no-cpu-baseline --no-e2e --no-train --no-density-sweep --no-alt --no-valu-floor --no-live-traffic --no-blocks"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o t -- $BENCH --steps 10 --warmup 2 --no-overlap > $O/bench_profiled.json 2> $O/trace.err
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o f -- $BENCH --steps 3 --warmup 1 > /dev/null 2> $O/pmc_fetch.err
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o w -- $BENCH --steps 3 --warmup 1 > /dev/null 2> $O/pmc_write.err
@@ -49,6 +49,6 @@ python3 tools/trace_one_forward.py $O/e2e_trace 60 > $O/${TAG}_e2e_one_forward.t
 python3 tools/trace_seq.py $O/e2e_trace > $O/${TAG}_e2e_sequence.txt 2>&1
 rm -rf $O/e2e_trace
 ./tools/ubench/softmax_rate.bin > $O/${TAG}_softmax_rate.txt 2>&1
-python3 bench.py > $O/${TAG}_bench.json 2> $O/bench.err
+python3 bench.py --full > $O/${TAG}_bench.json 2> $O/bench.err
 tail -1 $O/${TAG}_bench.json | cut -c1-600
 head -12 $O/${TAG}_bench_kernel_stats.csv | cut -c1-150

@@ -3,7 +3,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}; O=$R/gpurun_out/r05f; mkdir -p $O
 cd $R
 python3 -m pytest tests -m gpu -x -q > $O/gputests.txt 2>&1; grep -E "passed|failed" $O/gputests.txt | tail -2
 bash tools/sweep_spamat.sh 2>/dev/null | grep -v amdgpu > $O/sweep.txt; cat $O/sweep.txt | sed 's/algorithmic //'
-( time python3 bench.py > $O/bench.json 2> $O/bench.err ) 2> $O/bench.time; tail -3 $O/bench.time
+( time python3 bench.py --full > $O/bench.json 2> $O/bench.err ) 2> $O/bench.time; tail -3 $O/bench.time
 python3 - <<'PY'
 import json
 d=json.loads(open('gpurun_out/r05f/bench.json').read().strip().splitlines()[-1])
