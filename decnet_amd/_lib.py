@@ -84,7 +84,8 @@ class Stage0Params(ctypes.Structure):
 
 
 ERRORS = {-1: "null pointer", -2: "bad shape", -3: "shape not supported by the gfx950 kernels",
-          -4: "non-finite (NaN / Inf) element in a feature map (DECNET_CHECK_FINITE=1)"}
+          -4: "non-finite (NaN / Inf) element in a feature map (DECNET_CHECK_FINITE=1)",
+          -5: "library-format buffer not 16-byte aligned"}
 
 _lib = None
 

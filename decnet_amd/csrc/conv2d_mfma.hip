@@ -121,7 +121,7 @@ __device__ __forceinline__ void conv2d_mfma_store(const f32x4 (&acc)[TM][TN], co
                                                   int shuf) {
     const size_t HW = (size_t)H * W;
     const int xq = x0 + 4 * q;
-    const bool vec = (W & 3) == 0 && xq + 3 < W;
+    const bool vec = (W & 3) == 0 && ((uintptr_t)y & 15) == 0 && xq + 3 < W;   // y: any dense fp32 pointer
 #pragma unroll
     for (int nt = 0; nt < TN; ++nt) {
         const int n = (nt0 + nt) * 16 + r;
@@ -587,6 +587,7 @@ static int pack_impl(const float *w, void *w_packed, int Cin, int Cout, int k, i
 }
 
 int decnet_conv2d_mfma_pack_weight(const float *w, void *w_packed, int Cin, int Cout, int k, void *stream) {
+    if ((uintptr_t)w_packed & 15) return DECNET_ERR_MISALIGNED;       // read / written in 16-byte units
     if (acc2_mode()) return decnet_conv2d_mfma_pack_weight_acc2(w, w_packed, Cin, Cout, k, stream);
     return pack_impl(w, w_packed, Cin, Cout, k, 0, stream);
 }
@@ -598,6 +599,7 @@ size_t decnet_deconv2d_mfma_packed_bytes(int Cin, int Cout) {
 }
 
 int decnet_deconv2d_mfma_pack_weight(const float *w, void *w_packed, int Cin, int Cout, void *stream) {
+    if ((uintptr_t)w_packed & 15) return DECNET_ERR_MISALIGNED;       // read / written in 16-byte units
     if (acc2_mode()) return decnet_deconv2d_mfma_pack_weight_acc2(w, w_packed, Cin, Cout, stream);
     if (Cout < 1 || Cout > 7281) return DECNET_ERR_UNSUPPORTED;
     return pack_impl(w, w_packed, Cin, 9 * Cout, 1, 1, stream);
@@ -635,6 +637,7 @@ static int run_impl(const Segs &in, long Cin, const void *w_packed, const float 
 int decnet_conv2d_mfma_cat_bn_act(const float *const *xs, const int *cins, int nseg, const void *w_packed,
                                   const float *scale, const float *shift, float *y, int B, int Cout, int H, int W,
                                   int k, int dilation, int relu, void *stream) {
+    if ((uintptr_t)w_packed & 15) return DECNET_ERR_MISALIGNED;       // read / written in 16-byte units
     if (acc2_mode())
         return decnet_conv2d_mfma_cat_bn_act_acc2(xs, cins, nseg, w_packed, scale, shift, y, B, Cout, H, W, k, dilation, relu,
                                                   stream);
@@ -656,6 +659,7 @@ int decnet_conv2d_mfma_cat_bn_act(const float *const *xs, const int *cins, int n
 
 int decnet_deconv2d_mfma_k3s3_bn_act(const float *x, const void *w_packed, const float *scale, const float *shift,
                                      float *y, int B, int Cin, int Cout, int H, int W, int relu, void *stream) {
+    if ((uintptr_t)w_packed & 15) return DECNET_ERR_MISALIGNED;       // read / written in 16-byte units
     if (acc2_mode())
         return decnet_deconv2d_mfma_k3s3_bn_act_acc2(x, w_packed, scale, shift, y, B, Cin, Cout, H, W, relu, stream);
     if (!x || !w_packed || !scale || !shift || !y) return DECNET_ERR_NULL_POINTER;

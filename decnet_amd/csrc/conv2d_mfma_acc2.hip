@@ -154,7 +154,7 @@ __device__ __forceinline__ void conv2d_mfma_store(const f32x4 (&acc)[TM][TN], co
                                                   int shuf) {
     const size_t HW = (size_t)H * W;
     const int xq = x0 + 4 * q;
-    const bool vec = (W & 3) == 0 && xq + 3 < W;
+    const bool vec = (W & 3) == 0 && ((uintptr_t)y & 15) == 0 && xq + 3 < W;   // y: any dense fp32 pointer
 #pragma unroll
     for (int nt = 0; nt < TN; ++nt) {
         const int n = (nt0 + nt) * 16 + r;

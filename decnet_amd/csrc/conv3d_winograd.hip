@@ -1366,6 +1366,7 @@ int decnet_conv3d_wino_gemm(const float *V, const float *u, float *M, int nt, in
  * per-tap product + gather).  split: the bf16-term copy behind u has been written (decnet_tapconv_split_weight). */
 int decnet_tap_gemm(const float *V, const float *u, float *M, int P, int Ci, int Co, int ntaps, int split, void *stream) {
     if (!V || !u || !M) return DECNET_ERR_NULL_POINTER;
+    if (((uintptr_t)V | (uintptr_t)u | (uintptr_t)M) & 15) return DECNET_ERR_MISALIGNED;   // 16-byte operand loads / stores
     if (P < 1 || Ci < 1 || Co < 1 || ntaps < 1) return DECNET_ERR_BAD_SHAPE;
     if (Ci % 4 != 0 || Co > W_BN || (double)P * pad16(Ci > Co ? Ci : Co) * 4 * ntaps >= 2147483647.0 ||
         (double)ntaps * pad16(Ci) * W_BN * 4 >= 2147483647.0)
@@ -1385,6 +1386,7 @@ int decnet_tap_gemm(const float *V, const float *u, float *M, int P, int Ci, int
  * (u holds decnet_tapconv_weight_floats(Ci, ntaps) floats); decnet_tap_gemm reads it when Ci = 216. */
 int decnet_tapconv_split_weight(float *u, int Ci, int ntaps, void *stream) {
     if (!u) return DECNET_ERR_NULL_POINTER;
+    if ((uintptr_t)u & 15) return DECNET_ERR_MISALIGNED;
     if (Ci < 1 || ntaps < 1) return DECNET_ERR_BAD_SHAPE;
     const int KC = (Ci + 15) >> 4;
     const long nthr = (long)ntaps * ((KC + 1) / 2) * W_BN * 4;

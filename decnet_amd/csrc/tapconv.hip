@@ -109,6 +109,7 @@ size_t decnet_tapconv_chunk_floats(int B, int Ci, int H, int W) {
 
 int decnet_tapconv_to_chunks(const float *x, float *V, int B, int Ci, int H, int W, void *stream) {
     if (!x || !V) return DECNET_ERR_NULL_POINTER;
+    if ((uintptr_t)V & 15) return DECNET_ERR_MISALIGNED;              // float4 stores
     if (B < 1 || Ci < 1 || H < 1 || W < 1 || (double)B * H * W * Ci >= 2147483648.0) return DECNET_ERR_BAD_SHAPE;
     const size_t n = (size_t)B * H * W * ((Ci + 15) / 16);
     hipLaunchKernelGGL(nchw_to_chunks, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, V, Ci,
@@ -125,6 +126,7 @@ size_t decnet_tapconv_weight_floats(int Ci, int ntaps) {
 /* one branch: w [Co,Ci,k,k] (k = 1 or 3) -> taps tap0 .. tap0 + k*k - 1 of u */
 int decnet_tapconv_pack_weight(const float *w, float *u, int Co, int Ci, int k, int tap0, void *stream) {
     if (!w || !u) return DECNET_ERR_NULL_POINTER;
+    if ((uintptr_t)u & 15) return DECNET_ERR_MISALIGNED;              // read by decnet_tap_gemm in 16-byte units
     if (Co < 1 || Ci < 1 || tap0 < 0 || (k != 1 && k != 3)) return DECNET_ERR_BAD_SHAPE;
     if (Co > T_BN) return DECNET_ERR_UNSUPPORTED;
     const int n = k * k * T_BN * Ci;

@@ -43,6 +43,7 @@ extern "C" {
 #define DECNET_ERR_BAD_SHAPE (-2)     /* non-positive dim, max_disp < 1, index space > 2^31 */
 #define DECNET_ERR_UNSUPPORTED (-3)   /* shape does not fit the kernels' LDS tiling */
 #define DECNET_ERR_NONFINITE (-4)     /* DECNET_CHECK_FINITE=1 and a feature map holds a NaN / Inf (nothing launched) */
+#define DECNET_ERR_MISALIGNED (-5)    /* a library-format buffer (stated per entry) is not 16-byte aligned */
 
 /* Library / build identification: "decnet_hip <version> gfx950". */
 const char *decnet_version(void);
@@ -301,7 +302,10 @@ int decnet_conv2d_cat_epilogue(const float *const *xs, const int *cins, int nseg
  * submodule.py:245-343, 162-178; DynamicUpsampling.weight_learning :566-577; Refinement :690-717) on the bf16
  * matrix cores at fp32 accuracy (each fp32 operand split into three bf16 terms, six partial products): k = 1 or 3,
  * stride 1, padding dilation*(k/2), any Cin / Cout, input = channel concatenation of nseg (<= 6) tensors.
- * Weights: torch [Cout,Cin,k,k] packed once into decnet_conv2d_mfma_packed_bytes(...) bytes (0: unsupported). */
+ * Weights: torch [Cout,Cin,k,k] packed once into decnet_conv2d_mfma_packed_bytes(...) bytes (0: unsupported), a
+ * library-format buffer read in 16-byte units: 16-byte aligned, else DECNET_ERR_MISALIGNED (nothing launched; this holds
+ * for decnet_deconv2d_mfma_* below too).  k = 3 takes dilation <= 6: above that the halo tile of a workgroup does not
+ * fit the staging loop, and the call returns DECNET_ERR_UNSUPPORTED with nothing launched. */
 size_t decnet_conv2d_mfma_packed_bytes(int Cin, int Cout, int k);
 int decnet_conv2d_mfma_pack_weight(const float *w, void *w_packed, int Cin, int Cout, int k, void *stream);
 int decnet_conv2d_mfma_cat_bn_act(const float *const *xs, const int *cins, int nseg, const void *w_packed,
@@ -371,6 +375,9 @@ int decnet_deconv2d_k3s3_bn_act(const float *x, const float *w_packed, const flo
  *   decnet_tapconv_gather      y[b, br*Co+co, y, x] = act(scale * sum_t T[t][co][p + offset] + shift),
  *                              taps outside the image skipped; y [B, nbranch*Co, H, W]
  * Ci % 4 == 0, Co <= 224, nbranch <= 4.
+ * V, u and T are library-format buffers read and written in 16-byte units: they must be 16-byte aligned, else
+ * decnet_tapconv_to_chunks, _pack_weight, _split_weight and decnet_tap_gemm return DECNET_ERR_MISALIGNED with nothing
+ * launched (x, y, scale and shift may be any dense fp32 pointer; decnet_tapconv_gather reads T at any alignment).
  * ------------------------------------------------------------------------------------- */
 size_t decnet_tapconv_chunk_floats(int B, int Ci, int H, int W);
 int decnet_tapconv_to_chunks(const float *x, float *V, int B, int Ci, int H, int W, void *stream);
