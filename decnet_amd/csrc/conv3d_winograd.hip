@@ -1308,6 +1308,13 @@ int conv_stack(const float *x, const float *left, const float *right, const floa
     return DECNET_OK;
 }
 
+// the per-layer weights and the workspace (V / M / the residual plane) of the fused stack move in 16-byte units
+bool stack_misaligned(const float *const *u, int n_layers, const float *workspace) {
+    uintptr_t a = (uintptr_t)workspace;
+    for (int i = 0; i < n_layers; ++i) a |= (uintptr_t)u[i];
+    return (a & 15) != 0;
+}
+
 int variant_points(int variant) { return variant == 0 ? 64 : variant == 1 ? 144 : variant == 2 ? 216 : -1; }
 
 }  // namespace
@@ -1327,6 +1334,7 @@ size_t decnet_conv3d_wino_weight_floats(int Ci, int variant) {
 
 int decnet_conv3d_wino_pack_weight(const float *w, float *u, int Co, int Ci, int variant, void *stream) {
     if (!w || !u) return DECNET_ERR_NULL_POINTER;
+    if ((uintptr_t)u & 15) return DECNET_ERR_MISALIGNED;
     if (Co < 1 || Ci < 1 || variant_points(variant) < 0) return DECNET_ERR_BAD_SHAPE;
     if (Co > W_BN) return DECNET_ERR_UNSUPPORTED;
     const int n = Ci * W_BN;
@@ -1355,6 +1363,7 @@ int decnet_conv3d_wino_gemm(const float *V, const float *u, float *M, int nt, in
                             int variant, void *stream) {
     const int np = variant_points(variant);
     if (!V || !u || !M) return DECNET_ERR_NULL_POINTER;
+    if (((uintptr_t)V | (uintptr_t)u | (uintptr_t)M) & 15) return DECNET_ERR_MISALIGNED;   // 16-byte operand loads / stores
     if (nt < 1 || Ci < 1 || Co < 1 || np < 0) return DECNET_ERR_BAD_SHAPE;
     if (Ci % 4 != 0 || Co > W_BN || (double)nt * pad16(Ci > Co ? Ci : Co) * 4 * np >= 2147483647.0)
         return DECNET_ERR_UNSUPPORTED;
@@ -1427,6 +1436,7 @@ int decnet_conv3d_wino_stack_bn_act(const float *x, const float *const *u, const
     if (B < 1 || D < 1 || H < 1 || W < 1 || C < 1 || n_layers < 1) return DECNET_ERR_BAD_SHAPE;
     for (int i = 0; i < n_layers; ++i)
         if (!u[i] || !scale[i] || !shift[i]) return DECNET_ERR_NULL_POINTER;
+    if (stack_misaligned(u, n_layers, workspace)) return DECNET_ERR_MISALIGNED;
     if ((res_src < 0) != (res_dst < 0)) return DECNET_ERR_BAD_SHAPE;
     if (res_src >= 0 && !(res_src < res_dst && res_dst < n_layers - 1)) return DECNET_ERR_UNSUPPORTED;
     if (n_layers < 2 || !stack_ok(B, D, H, W, C, variant)) return DECNET_ERR_UNSUPPORTED;
@@ -1457,6 +1467,7 @@ int decnet_costvol_wino_stack_bn_act_cf(const float *left, const float *right, c
     if (H < 2 || W < 2) return DECNET_ERR_UNSUPPORTED;   // the stretched warp of one row / column: per-layer path
     for (int i = 0; i < n_layers; ++i)
         if (!u[i] || !scale[i] || !shift[i]) return DECNET_ERR_NULL_POINTER;
+    if (stack_misaligned(u, n_layers, workspace)) return DECNET_ERR_MISALIGNED;
     if ((res_src < 0) != (res_dst < 0)) return DECNET_ERR_BAD_SHAPE;
     if (res_src >= 0 && !(res_src < res_dst && res_dst < n_layers - 1)) return DECNET_ERR_UNSUPPORTED;
     static const int off = [] { const char *e = getenv("DECNET_WINO_HEAD"); return e && !strcmp(e, "0") ? 1 : 0; }();
@@ -1471,6 +1482,7 @@ int decnet_conv3d_wino_bn_act(const float *x, const float *u, const float *scale
                               const float *residual, float *y, float *workspace, int B, int D, int H,
                               int W, int Ci, int Co, int relu, int variant, void *stream) {
     if (!x || !u || !scale || !shift || !y || !workspace) return DECNET_ERR_NULL_POINTER;
+    if (((uintptr_t)u | (uintptr_t)workspace) & 15) return DECNET_ERR_MISALIGNED;   // V / M move in 16-byte units
     if (B < 1 || D < 1 || H < 1 || W < 1 || Ci < 1 || Co < 1 || variant_points(variant) < 0)
         return DECNET_ERR_BAD_SHAPE;
     if (Ci % 4 != 0 || Co > W_BN) return DECNET_ERR_UNSUPPORTED;

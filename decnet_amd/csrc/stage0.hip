@@ -702,6 +702,7 @@ int decnet_conv3d_packed_cout(int Co) { return Co >= 1 && Co <= CONV_BN ? CONV_B
 
 int decnet_conv3d_pack_weight(const float *w, float *wp, int Co, int Ci, void *stream) {
     if (!w || !wp) return DECNET_ERR_NULL_POINTER;
+    if ((uintptr_t)wp & 15) return DECNET_ERR_MISALIGNED;       // read as float4 by conv3d_k3_igemm
     if (Co < 1 || Ci < 1) return DECNET_ERR_BAD_SHAPE;
     if (Co > CONV_BN) return DECNET_ERR_UNSUPPORTED;
     size_t total = (size_t)27 * Ci * CONV_BN;
@@ -714,6 +715,7 @@ int decnet_conv3d_bn_act(const float *x, const float *wp, const float *scale, co
                          const float *residual, float *y, int B, int D, int H, int W, int Ci,
                          int Co, int relu, void *stream) {
     if (!x || !wp || !scale || !shift || !y) return DECNET_ERR_NULL_POINTER;
+    if ((uintptr_t)wp & 15) return DECNET_ERR_MISALIGNED;
     if (B < 1 || D < 1 || H < 1 || W < 1 || Ci < 1 || Co < 1) return DECNET_ERR_BAD_SHAPE;
     if (D > 1023 || H > 1023 || W > 1023) return DECNET_ERR_UNSUPPORTED;
     if (Ci % 4 != 0 || Co > CONV_BN) return DECNET_ERR_UNSUPPORTED;
@@ -763,6 +765,7 @@ int decnet_conv3d_cout1_softargmax_ws(const float *x, const float *w, float scal
                                       float *reg, float *pred, float *workspace, int B, int D, int H,
                                       int W, int Ci, void *stream) {
     if (!x || !w || !pred || !workspace) return DECNET_ERR_NULL_POINTER;
+    if ((uintptr_t)workspace & 15) return DECNET_ERR_MISALIGNED;    // T is stored as f32x4
     if (B < 1 || D < 1 || H < 1 || W < 1 || Ci < 1) return DECNET_ERR_BAD_SHAPE;
     const double Md = (double)B * D * H * W;
     if (Ci % 4 != 0 || Ci > 256 || D > 256 || Md * Ci * 4 >= 2147483647.0) return DECNET_ERR_UNSUPPORTED;

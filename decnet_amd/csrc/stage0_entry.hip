@@ -13,6 +13,7 @@ namespace {
 // the algorithm the Python side picks too (stage0.py:conv_algo): F(4,3)^3 where depth tiles of 4 pay
 inline int auto_variant(int D) { return 216 * ((D + 3) / 4) <= 0.92 * 144 * ((D + 1) / 2) ? 2 : 1; }
 inline size_t align64(size_t n) { return (n + 63) & ~(size_t)63; }
+constexpr size_t WS_SLACK = 4;      // floats: room to move the workspace base up to a 16-byte boundary
 }  // namespace
 
 // csrc/stage0.hip (library-internal)
@@ -43,7 +44,8 @@ size_t decnet_stage0_workspace_floats(int B, int C, int H, int W, int D, int var
     // cost volume + three activation buffers (+ the Winograd V/M scratch); the last layer's tap products
     // (decnet_conv3d_cout1_workspace_floats) reuse an activation buffer that is free by then when they fit
     const size_t last = decnet_conv3d_cout1_workspace_floats(B, D, H, W);
-    return 4 * act + align64(wino) + (last > act ? align64(last) : 0);
+    // + WS_SLACK: the entry starts its buffers at the first 16-byte boundary of the workspace (any alignment is accepted)
+    return 4 * act + align64(wino) + (last > act ? align64(last) : 0) + WS_SLACK;
 }
 
 int decnet_stage0_forward(const float *left, const float *right, const decnet_stage0_params *p,
@@ -62,12 +64,18 @@ int decnet_stage0_forward_cf(const float *left, const float *right, const decnet
     if (cost_func == DECNET_COST_CAT && !w_pre) return DECNET_ERR_NULL_POINTER;
     for (int i = 0; i < 7; ++i)
         if (!p->w[i] || !p->scale[i] || !p->shift[i]) return DECNET_ERR_NULL_POINTER;
+    // the packed weights move in 16-byte units (the workspace may sit anywhere: its buffers start at its first 16-byte
+    // boundary, within the WS_SLACK floats decnet_stage0_workspace_floats adds)
+    uintptr_t lib_fmt = 0;
+    for (int i = 0; i < 7; ++i) lib_fmt |= (uintptr_t)p->w[i];
+    if (lib_fmt & 15) return DECNET_ERR_MISALIGNED;
     if (B < 1 || C < 1 || H < 1 || W < 1 || D < 1 || variant < -1 || variant > 3) return DECNET_ERR_BAD_SHAPE;
     if (C % 4) return DECNET_ERR_UNSUPPORTED;          // channel counts move in 16-byte groups (pad to x4)
     if (variant < 0) variant = auto_variant(D);
     if (!decnet_stage0_cf_workspace_floats(B, C, H, W, D, variant, cost_func)) return DECNET_ERR_UNSUPPORTED;
     const size_t act = align64((size_t)B * D * H * W * C);
-    float *cv = workspace, *a = cv + act, *b = a + act, *c = b + act, *ws = c + act;
+    float *cv = reinterpret_cast<float *>(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
+    float *a = cv + act, *b = a + act, *c = b + act, *ws = c + act;
     const size_t stack = variant <= 2 ? decnet_conv3d_wino_stack_workspace_floats(B, D, H, W, C, variant) : 0;
     size_t wino = variant <= 2 ? decnet_conv3d_wino_workspace_floats(B, D, H, W, C, C, variant) : 0;
     wino = align64(stack > wino ? stack : wino);

@@ -141,7 +141,9 @@ int decnet_conv3d_pointwise(const float *x, const float *w, float *y, int B, int
                             int channels_last, void *stream);
 
 /* Repack one Conv3d weight  [Co,Ci,3,3,3] (torch layout, submodule.py:109) into the kernels'
- * [27, Ci, CoP] layout, CoP = decnet_conv3d_packed_cout(Co), zero padded.                  */
+ * [27, Ci, CoP] layout, CoP = decnet_conv3d_packed_cout(Co), zero padded.  w_packed is a library-format buffer read in
+ * 16-byte units: 16-byte aligned, else decnet_conv3d_pack_weight and decnet_conv3d_bn_act return DECNET_ERR_MISALIGNED
+ * (nothing launched).                                                                       */
 int decnet_conv3d_packed_cout(int Co);
 int decnet_conv3d_pack_weight(const float *w_oidhw, float *w_packed, int Co, int Ci,
                               void *stream);
@@ -166,7 +168,10 @@ int decnet_conv3d_bn_act(const float *x, const float *w_packed, const float *sca
  *              [Co,Ci,3,3,3] -> U^T [points][ceil(Ci/16)][224][16]
  *              (decnet_conv3d_wino_weight_floats floats)
  *   workspace  decnet_conv3d_wino_workspace_floats(...) floats of device scratch
- *   everything else as decnet_conv3d_bn_act.                                                */
+ *   everything else as decnet_conv3d_bn_act.
+ * u, workspace and the V / M of decnet_conv3d_wino_gemm are library-format buffers moved in 16-byte units: 16-byte
+ * aligned, else DECNET_ERR_MISALIGNED (nothing launched; the stack entries below check every u[i] and their workspace
+ * too).  x, y, residual, scale and shift may be any dense fp32 pointer.                    */
 size_t decnet_conv3d_wino_weight_floats(int Ci, int variant);
 int decnet_conv3d_wino_pack_weight(const float *w_oidhw, float *u, int Co, int Ci, int variant,
                                    void *stream);
@@ -216,7 +221,8 @@ int decnet_conv3d_cout1_softargmax(const float *x, const float *w_oidhw, float s
 
 /* The same operator in two passes (a [positions x Ci] x [Ci x 27] product on the matrix cores, then
  * a 27-tap gather + soft-argmax) that read x once instead of 27 times.  workspace:
- * decnet_conv3d_cout1_workspace_floats(B,D,H,W) floats of device scratch.  Ci <= 256, D <= 256. */
+ * decnet_conv3d_cout1_workspace_floats(B,D,H,W) floats of device scratch, 16-byte aligned (else DECNET_ERR_MISALIGNED,
+ * nothing launched).  Ci <= 256, D <= 256. */
 size_t decnet_conv3d_cout1_workspace_floats(int B, int D, int H, int W);
 int decnet_conv3d_cout1_softargmax_ws(const float *x, const float *w_oidhw, float scale,
                                       float shift, float *reg, float *pred, float *workspace,
@@ -233,7 +239,10 @@ int decnet_conv3d_cout1_softargmax_ws(const float *x, const float *w_oidhw, floa
  *               folded BatchNorm3d [C]; the last layer: w_last [1,C,3,3,3] (torch layout), scale_last, shift_last
  *   variant     -1 = automatic (F(4,3)^3 where depth tiles of 4 pay, else F(2,3)xF(4,3)^2), else as above
  *   workspace   decnet_stage0_workspace_floats(B,C,H,W,D,variant) floats of device scratch (cost volume,
- *               three ping-pong activation buffers, the Winograd intermediates); contents are scratch
+ *               three ping-pong activation buffers, the Winograd intermediates); contents are scratch.  Any
+ *               float alignment: the entry starts its buffers at the first 16-byte boundary inside it.
+ *               The seven packed w[i] must be 16-byte aligned, else DECNET_ERR_MISALIGNED
+ *               (nothing launched; decnet_stage0_forward_cf too)
  *   reg         NULL or [B,D,H,W]: the regularised volume (what CostRegNetNoDown returns)
  *   pred        [B,H,W]: the stage-0 disparity
  * C must be a multiple of 4 (pad features and weights with zero channels otherwise).             */
