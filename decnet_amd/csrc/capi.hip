@@ -26,7 +26,7 @@ int decnet_mfma_backward(int var, const float *ref, const float *tar, const floa
                          float *grad_ref, float *grad_tar, float *grad_disp, int B, int C, int H,
                          int W, int max_disp, hipStream_t stream);
 
-// spamat_wide.hip: disparity ranges wider than 18 tiles (max_disp > 272) as several band-kernel calls + per-pixel merges
+// spamat_wide.hip: disparity ranges wider than 18 tiles (max_disp > 273) as several band-kernel calls + per-pixel merges
 int decnet_wide_forward(int mode, const float *ref, const float *tar, const float *rmask, const float *tmask,
                         const float *disparity, float *out, float *var_out, float *sum_sim, float *max_cost, int B, int C,
                         int H, int W, int D, int allow_compact, int mbits, hipStream_t stream);
@@ -193,7 +193,7 @@ int decnet_spamatvar_forward_bits(const float *ref, const float *tar, const unsi
     const void *p[] = {ref, tar, ref_bits, tar_bits, output, variance, sum_similarities, max_cost};
     int rc = decnet_check_spamat_args(p, 8, B, C, H, W, max_disp);
     if (rc) return rc;
-    // the matrix-core kernels only (the row-tile fallback reads float planes); above max_disp 272 (18 tiles) band by
+    // the matrix-core kernels only (the row-tile fallback reads float planes); above max_disp 273 (18 tiles) band by
     // band on masks unpacked into scratch planes (spamat_wide.hip; UNSUPPORTED while the stream is being captured).
     // DECNET_SPAMAT_KERNEL=rowtile pins a kernel this entry does not have -> UNSUPPORTED, the caller falls back to the
     // float-mask entry (decnet_amd.model does)

@@ -1539,7 +1539,7 @@ int launch_kq(int mode, const float *ref, const float *tar, const float *rmask, 
 }  // namespace
 
 // mode: 0 SpaMat, 1 SpaVar, 2 fused.  Returns DECNET_ERR_UNSUPPORTED when the band needs more
-// than 18 tiles (max_disp > 272) or a tile does not fit LDS; the dispatcher in capi.hip then
+// than 18 tiles (max_disp > 273) or a tile does not fit LDS; the dispatcher in capi.hip then
 // uses the row-tile kernel.  allow_compact = 0 pins the dense path (A/B benchmarks, tests).
 // mbits = 1: rmask / tmask point at bit-packed masks ([B,H,ceil(W/64)] 64-bit words, decnet_detail_mask's layout).
 int decnet_mfma_forward(int mode, const float *ref, const float *tar, const float *rmask,
@@ -1551,12 +1551,12 @@ int decnet_mfma_forward(int mode, const float *ref, const float *tar, const floa
 #define GO(N)                                                                                     \
     return launch_kq<N>(mode, ref, tar, rmask, tmask, disparity, out, var_out, sum_sim, max_cost, \
                         B, C, H, W, D, allow_compact, mbits, stream)
-    if (need <= 3) GO(3);       // D <= 32   (stage 1: 24, 30)
-    if (need <= 6) GO(6);       // D <= 80   (stage 2: 72)
-    if (need <= 8) GO(8);       // D <= 112  (stage 2 at max_disp 270: 90)
-    if (need <= 11) GO(11);     // D <= 160
-    if (need <= 15) GO(15);     // D <= 224  (stage 3: 216)
-    if (need <= 18) GO(18);     // D <= 272  (stage 3 at max_disp 270)
+    if (need <= 3) GO(3);       // D <= 33   (stage 1: 24, 30)
+    if (need <= 6) GO(6);       // D <= 81   (stage 2: 72)
+    if (need <= 8) GO(8);       // D <= 113  (stage 2 at max_disp 270: 90)
+    if (need <= 11) GO(11);     // D <= 161
+    if (need <= 15) GO(15);     // D <= 225  (stage 3: 216)
+    if (need <= 18) GO(18);     // D <= 273  (stage 3 at max_disp 270)
     return DECNET_ERR_UNSUPPORTED;
 #undef GO
 }

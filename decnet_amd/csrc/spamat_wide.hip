@@ -1,5 +1,5 @@
 // decnet_amd/csrc/spamat_wide.hip -- SpaMat / SpaVar for disparity ranges wider than the band kernels' 18 tiles
-// (max_disp > 272: the reference's own demo data carries ndisp 400 / 610 -> max_disp 405 / 621 at stage 3,
+// (max_disp > 273: the reference's own demo data carries ndisp 400 / 610 -> max_disp 405 / 621 at stage 3,
 // demo.py:149-155), forward and backward, on the matrix-core kernels instead of the VALU row-tile fallback.
 //
 // The candidate range [0, D) is cut into nb = ceil(D / 272) bands [d0, d0 + Db).  Band b is an ordinary call of the band

@@ -1,7 +1,7 @@
 """Guarded placement of device buffers for the edge tests through the C ABI (tests/test_trunk_edges_gpu.py,
 tests/test_stage0_edges_gpu.py): every buffer is a window of a larger one, filled with a sentinel outside the window,
-16-byte aligned or at an odd float offset; `Place.check` verifies margins, unmodified inputs and fully written outputs,
-`_both` runs a case at both placements and requires bit-identical results."""
+16-byte aligned or at an odd float offset; `Place.check` verifies margins, unmodified inputs and fully written outputs
+(`Place.check_untouched`: outputs left alone by a rejected call), `_both` runs a case at both placements and requires bit-identical results."""
 import ctypes
 import math
 
@@ -92,6 +92,16 @@ class Place:
                     "%s: an input was modified" % what
             elif kind == "out" and win.dtype == torch.float32:
                 assert not bool(torch.isnan(win).any()), "%s: output element not written" % what
+
+
+    def check_untouched(self, what):
+        """For calls that must launch nothing: margins intact and every output window still holds its NaN pre-fill."""
+        torch.cuda.synchronize()
+        for kind, buf, n, _ in self.items:
+            assert bool((buf[:self.off] == SENT).all()) and bool((buf[self.off + n:] == SENT).all()), \
+                "%s: write outside a %s window" % (what, kind)
+            if kind == "out":
+                assert bool(torch.isnan(buf[self.off:self.off + n]).all()), "%s: an output was written" % what
 
 
 def _bn(cout, g, big=1.0):
