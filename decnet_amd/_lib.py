@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("DECNET_HIP_LIB", _DEFAULT_LIB)
 _P = ctypes.c_void_p
 _I = ctypes.c_int
 _F = ctypes.c_float
+_Z = ctypes.c_size_t
 
 # name -> argtypes  (kept in the order of include/decnet_hip.h; tests check every symbol)
 SIGNATURES = {
@@ -22,6 +23,13 @@ SIGNATURES = {
     "decnet_spavar_backward": [_P] * 12 + [_I] * 5 + [_P],
     "decnet_spamatvar_forward": [_P] * 8 + [_I] * 5 + [_P],
     "decnet_spamatvar_forward_bits": [_P] * 8 + [_I] * 5 + [_P],
+    "decnet_spamat_workspace_floats": [_I] * 6,
+    "decnet_spamat_forward_ws": [_P] * 7 + [_I] * 5 + [_P, _Z, _P],
+    "decnet_spamat_backward_ws": [_P] * 10 + [_I] * 5 + [_P, _Z, _P],
+    "decnet_spavar_forward_ws": [_P] * 8 + [_I] * 5 + [_P, _Z, _P],
+    "decnet_spavar_backward_ws": [_P] * 12 + [_I] * 5 + [_P, _Z, _P],
+    "decnet_spamatvar_forward_ws": [_P] * 8 + [_I] * 5 + [_P, _Z, _P],
+    "decnet_spamatvar_forward_bits_ws": [_P] * 8 + [_I] * 5 + [_P, _Z, _P],
     "decnet_costvol_forward": [_P] * 3 + [_I] * 5 + [_P],
     "decnet_costvol_forward_cf": [_P] * 3 + [_I] * 6 + [_P],
     "decnet_conv3d_pointwise": [_P] * 3 + [_I] * 6 + [_P],

@@ -26,14 +26,17 @@ int decnet_mfma_backward(int var, const float *ref, const float *tar, const floa
                          float *grad_ref, float *grad_tar, float *grad_disp, int B, int C, int H,
                          int W, int max_disp, hipStream_t stream);
 
-// spamat_wide.hip: disparity ranges wider than 18 tiles (max_disp > 273) as several band-kernel calls + per-pixel merges
+// spamat_wide.hip: disparity ranges wider than 18 tiles (max_disp > 273) as several band-kernel calls + per-pixel merges.
+// ws: the caller's workspace of decnet_wide_workspace_floats floats (the `_ws` entries), or nullptr (the legacy entries: the
+// sweep allocates its scratch, and is UNSUPPORTED while the stream is being captured)
 int decnet_wide_forward(int mode, const float *ref, const float *tar, const float *rmask, const float *tmask,
                         const float *disparity, float *out, float *var_out, float *sum_sim, float *max_cost, int B, int C,
-                        int H, int W, int D, int allow_compact, int mbits, hipStream_t stream);
+                        int H, int W, int D, int allow_compact, int mbits, float *ws, hipStream_t stream);
 int decnet_wide_backward(int var, const float *ref, const float *tar, const float *rmask, const float *tmask,
                          const float *disparity, const float *out, const float *sum_sim, const float *max_cost,
                          const float *grad_out, float *grad_ref, float *grad_tar, float *grad_disp, int B, int C, int H,
-                         int W, int D, hipStream_t stream);
+                         int W, int D, float *ws, hipStream_t stream);
+size_t decnet_wide_workspace_floats(int B, int C, int H, int W, int D, int which);
 
 #include <stdlib.h>
 #include <string.h>
@@ -104,12 +107,13 @@ static int check_finite(const float *ref, const float *tar, int B, int C, int H,
     return h ? DECNET_ERR_NONFINITE : 0;
 }
 
-// Backward dispatch: matrix-core kernels, row-tile kernels for what they do not cover.
+// Backward dispatch: matrix-core kernels, row-tile kernels for what they do not cover.  ws: the wide sweep's scratch from
+// the caller (the `_ws` entries, checked by check_workspace), or nullptr (the legacy entries).
 static int backward_dispatch(int var, const float *ref, const float *tar, const float *rmask,
                              const float *tmask, const float *disparity, const float *out,
                              const float *sum_sim, const float *max_cost, const float *grad_out,
                              float *grad_ref, float *grad_tar, float *grad_disp, int B, int C, int H,
-                             int W, int max_disp, hipStream_t stream) {
+                             int W, int max_disp, float *ws, hipStream_t stream) {
     const int pinned = spamat_pinned();
     if (pinned != 1) {
         int rc = decnet_mfma_backward(var, ref, tar, rmask, tmask, disparity, out, sum_sim, max_cost,
@@ -117,7 +121,7 @@ static int backward_dispatch(int var, const float *ref, const float *tar, const 
                                       stream);
         if (rc == DECNET_ERR_UNSUPPORTED && max_disp > 272)       // wider than 18 tiles: the same kernels band by band
             rc = decnet_wide_backward(var, ref, tar, rmask, tmask, disparity, out, sum_sim, max_cost, grad_out, grad_ref,
-                                      grad_tar, grad_disp, B, C, H, W, max_disp, stream);
+                                      grad_tar, grad_disp, B, C, H, W, max_disp, ws, stream);
         if (rc != DECNET_ERR_UNSUPPORTED || pinned >= 2) return rc;
     }
     return decnet_rowtile_backward(var, ref, tar, rmask, tmask, disparity, out, sum_sim, max_cost,
@@ -132,7 +136,7 @@ static int backward_dispatch(int var, const float *ref, const float *tar, const 
 static int forward_dispatch(int mode, const float *ref, const float *tar, const float *rmask,
                             const float *tmask, const float *disparity, float *out, float *var_out,
                             float *sum_sim, float *max_cost, int B, int C, int H, int W,
-                            int max_disp, hipStream_t stream) {
+                            int max_disp, float *ws, hipStream_t stream) {
     const int pinned = spamat_pinned();
     if (int rc = check_finite(ref, tar, B, C, H, W, stream)) return rc;
     if (pinned != 1) {
@@ -140,61 +144,86 @@ static int forward_dispatch(int mode, const float *ref, const float *tar, const 
                                      max_cost, B, C, H, W, max_disp, pinned != 3, 0, stream);
         if (rc == DECNET_ERR_UNSUPPORTED && max_disp > 272)       // wider than 18 tiles: the same kernels band by band
             rc = decnet_wide_forward(mode, ref, tar, rmask, tmask, disparity, out, var_out, sum_sim, max_cost, B, C, H, W,
-                                     max_disp, pinned != 3, 0, stream);
+                                     max_disp, pinned != 3, 0, ws, stream);
         if (rc != DECNET_ERR_UNSUPPORTED || pinned >= 2) return rc;
     }
     return decnet_rowtile_forward(mode, ref, tar, rmask, tmask, disparity, out, var_out, sum_sim,
                                   max_cost, B, C, H, W, max_disp, stream);
 }
 
-extern "C" {
+// ---- the caller-workspace (`_ws`) entries ------------------------------------------------------------------------------
+// workspace floats of entry `which` (include/decnet_hip.h); 0 for bad shapes and wherever one band takes the call
+static size_t workspace_floats(int B, int C, int H, int W, int max_disp, int which) {
+    if (B < 1 || C < 1 || H < 1 || W < 1 || max_disp < 1 || (double)B * C * H * W >= 2147483648.0) return 0;
+    return decnet_wide_workspace_floats(B, C, H, W, max_disp, which);
+}
+// Scratch of one call.  legacy(): the six original entries (the sweep allocates).  A `_ws` entry passes what its caller
+// gave; check() then is the workspace contract of the header, before anything is launched.
+struct Workspace {
+    float *p;
+    size_t floats;
+    bool given;
+    static Workspace legacy() { return Workspace{nullptr, 0, false}; }
+    int check(int B, int C, int H, int W, int max_disp, int which) {
+        const size_t need = given ? workspace_floats(B, C, H, W, max_disp, which) : 0;
+        if (!need) {                    // one band (or a legacy entry): exactly the existing entry
+            p = nullptr;
+            return DECNET_OK;
+        }
+        if (!p) return DECNET_ERR_NULL_POINTER;
+        if (floats < need) return DECNET_ERR_BAD_SHAPE;
+        if ((uintptr_t)p & 15) return DECNET_ERR_MISALIGNED;
+        return DECNET_OK;
+    }
+};
 
-const char *decnet_version(void) { return "decnet_hip 0.1.0 gfx950"; }
-
-int decnet_spamat_forward(const float *ref, const float *tar, const float *ref_mask,
-                          const float *tar_mask, float *output, float *sum_similarities,
-                          float *max_cost, int B, int C, int H, int W, int max_disp, void *stream) {
+static int spamat_forward(const float *ref, const float *tar, const float *ref_mask, const float *tar_mask, float *output,
+                          float *sum_similarities, float *max_cost, int B, int C, int H, int W, int max_disp, Workspace ws,
+                          void *stream) {
     const void *p[] = {ref, tar, ref_mask, tar_mask, output, sum_similarities, max_cost};
     int rc = decnet_check_spamat_args(p, 7, B, C, H, W, max_disp);
     if (rc) return rc;
+    if ((rc = ws.check(B, C, H, W, max_disp, 0))) return rc;
     return forward_dispatch(0, ref, tar, ref_mask, tar_mask, nullptr, output, nullptr,
-                                  sum_similarities, max_cost, B, C, H, W, max_disp,
+                                  sum_similarities, max_cost, B, C, H, W, max_disp, ws.p,
                                   (hipStream_t)stream);
 }
 
-int decnet_spavar_forward(const float *ref, const float *tar, const float *ref_mask,
-                          const float *tar_mask, const float *disparity, float *output,
-                          float *sum_similarities, float *max_cost, int B, int C, int H, int W,
-                          int max_disp, void *stream) {
+static int spavar_forward(const float *ref, const float *tar, const float *ref_mask, const float *tar_mask,
+                          const float *disparity, float *output, float *sum_similarities, float *max_cost, int B, int C,
+                          int H, int W, int max_disp, Workspace ws, void *stream) {
     const void *p[] = {ref, tar, ref_mask, tar_mask, disparity, output, sum_similarities, max_cost};
     int rc = decnet_check_spamat_args(p, 8, B, C, H, W, max_disp);
     if (rc) return rc;
+    if ((rc = ws.check(B, C, H, W, max_disp, 1))) return rc;
     return forward_dispatch(1, ref, tar, ref_mask, tar_mask, disparity, nullptr, output,
-                                  sum_similarities, max_cost, B, C, H, W, max_disp,
+                                  sum_similarities, max_cost, B, C, H, W, max_disp, ws.p,
                                   (hipStream_t)stream);
 }
 
-int decnet_spamatvar_forward(const float *ref, const float *tar, const float *ref_mask,
-                             const float *tar_mask, float *output, float *variance,
-                             float *sum_similarities, float *max_cost, int B, int C, int H, int W,
-                             int max_disp, void *stream) {
+static int spamatvar_forward(const float *ref, const float *tar, const float *ref_mask, const float *tar_mask,
+                             float *output, float *variance, float *sum_similarities, float *max_cost, int B, int C, int H,
+                             int W, int max_disp, Workspace ws, void *stream) {
     const void *p[] = {ref, tar, ref_mask, tar_mask, output, variance, sum_similarities, max_cost};
     int rc = decnet_check_spamat_args(p, 8, B, C, H, W, max_disp);
     if (rc) return rc;
+    if ((rc = ws.check(B, C, H, W, max_disp, 2))) return rc;
     return forward_dispatch(2, ref, tar, ref_mask, tar_mask, nullptr, output, variance,
-                                  sum_similarities, max_cost, B, C, H, W, max_disp,
+                                  sum_similarities, max_cost, B, C, H, W, max_disp, ws.p,
                                   (hipStream_t)stream);
 }
 
-int decnet_spamatvar_forward_bits(const float *ref, const float *tar, const unsigned long long *ref_bits,
+static int spamatvar_forward_bits(const float *ref, const float *tar, const unsigned long long *ref_bits,
                                   const unsigned long long *tar_bits, float *output, float *variance,
-                                  float *sum_similarities, float *max_cost, int B, int C, int H, int W,
-                                  int max_disp, void *stream) {
+                                  float *sum_similarities, float *max_cost, int B, int C, int H, int W, int max_disp,
+                                  Workspace ws, void *stream) {
     const void *p[] = {ref, tar, ref_bits, tar_bits, output, variance, sum_similarities, max_cost};
     int rc = decnet_check_spamat_args(p, 8, B, C, H, W, max_disp);
     if (rc) return rc;
+    if ((rc = ws.check(B, C, H, W, max_disp, 3))) return rc;
     // the matrix-core kernels only (the row-tile fallback reads float planes); above max_disp 273 (18 tiles) band by
-    // band on masks unpacked into scratch planes (spamat_wide.hip; UNSUPPORTED while the stream is being captured).
+    // band with the masks unpacked into scratch planes (spamat_wide.hip; the legacy entry, whose sweep allocates, is
+    // UNSUPPORTED there while the stream is being captured; the `_ws` entry is not).
     // DECNET_SPAMAT_KERNEL=rowtile pins a kernel this entry does not have -> UNSUPPORTED, the caller falls back to the
     // float-mask entry (decnet_amd.model does)
     if (spamat_pinned() == 1) return DECNET_ERR_UNSUPPORTED;
@@ -206,8 +235,71 @@ int decnet_spamatvar_forward_bits(const float *ref, const float *tar, const unsi
     if (rc == DECNET_ERR_UNSUPPORTED && max_disp > 272)
         rc = decnet_wide_forward(2, ref, tar, reinterpret_cast<const float *>(ref_bits),
                                  reinterpret_cast<const float *>(tar_bits), nullptr, output, variance, sum_similarities,
-                                 max_cost, B, C, H, W, max_disp, spamat_pinned() != 3, 1, (hipStream_t)stream);
+                                 max_cost, B, C, H, W, max_disp, spamat_pinned() != 3, 1, ws.p, (hipStream_t)stream);
     return rc;
+}
+
+static int spamat_backward(const float *ref, const float *tar, const float *ref_mask, const float *tar_mask,
+                           const float *output, const float *sum_similarities, const float *max_cost,
+                           const float *grad_output, float *grad_ref, float *grad_tar, int B, int C, int H, int W,
+                           int max_disp, Workspace ws, void *stream) {
+    const void *p[] = {ref, tar, ref_mask, tar_mask, output, sum_similarities, max_cost,
+                       grad_output, grad_ref, grad_tar};
+    int rc = decnet_check_spamat_args(p, 10, B, C, H, W, max_disp);
+    if (rc) return rc;
+    if ((rc = ws.check(B, C, H, W, max_disp, 4))) return rc;
+    return backward_dispatch(0, ref, tar, ref_mask, tar_mask, nullptr, output,
+                                   sum_similarities, max_cost, grad_output, grad_ref, grad_tar,
+                                   nullptr, B, C, H, W, max_disp, ws.p, (hipStream_t)stream);
+}
+
+static int spavar_backward(const float *ref, const float *tar, const float *ref_mask, const float *tar_mask,
+                           const float *disparity, const float *output, const float *sum_similarities,
+                           const float *max_cost, const float *grad_output, float *grad_ref, float *grad_tar,
+                           float *grad_disparity, int B, int C, int H, int W, int max_disp, Workspace ws, void *stream) {
+    const void *p[] = {ref, tar, ref_mask, tar_mask, disparity, output, sum_similarities, max_cost,
+                       grad_output, grad_ref, grad_tar, grad_disparity};
+    int rc = decnet_check_spamat_args(p, 12, B, C, H, W, max_disp);
+    if (rc) return rc;
+    if ((rc = ws.check(B, C, H, W, max_disp, 5))) return rc;
+    return backward_dispatch(1, ref, tar, ref_mask, tar_mask, disparity, output,
+                                   sum_similarities, max_cost, grad_output, grad_ref, grad_tar,
+                                   grad_disparity, B, C, H, W, max_disp, ws.p, (hipStream_t)stream);
+}
+
+extern "C" {
+
+const char *decnet_version(void) { return "decnet_hip 0.1.0 gfx950"; }
+
+int decnet_spamat_forward(const float *ref, const float *tar, const float *ref_mask,
+                          const float *tar_mask, float *output, float *sum_similarities,
+                          float *max_cost, int B, int C, int H, int W, int max_disp, void *stream) {
+    return spamat_forward(ref, tar, ref_mask, tar_mask, output, sum_similarities, max_cost, B, C, H, W, max_disp,
+                          Workspace::legacy(), stream);
+}
+
+int decnet_spavar_forward(const float *ref, const float *tar, const float *ref_mask,
+                          const float *tar_mask, const float *disparity, float *output,
+                          float *sum_similarities, float *max_cost, int B, int C, int H, int W,
+                          int max_disp, void *stream) {
+    return spavar_forward(ref, tar, ref_mask, tar_mask, disparity, output, sum_similarities, max_cost, B, C, H, W,
+                          max_disp, Workspace::legacy(), stream);
+}
+
+int decnet_spamatvar_forward(const float *ref, const float *tar, const float *ref_mask,
+                             const float *tar_mask, float *output, float *variance,
+                             float *sum_similarities, float *max_cost, int B, int C, int H, int W,
+                             int max_disp, void *stream) {
+    return spamatvar_forward(ref, tar, ref_mask, tar_mask, output, variance, sum_similarities, max_cost, B, C, H, W,
+                             max_disp, Workspace::legacy(), stream);
+}
+
+int decnet_spamatvar_forward_bits(const float *ref, const float *tar, const unsigned long long *ref_bits,
+                                  const unsigned long long *tar_bits, float *output, float *variance,
+                                  float *sum_similarities, float *max_cost, int B, int C, int H, int W,
+                                  int max_disp, void *stream) {
+    return spamatvar_forward_bits(ref, tar, ref_bits, tar_bits, output, variance, sum_similarities, max_cost, B, C, H, W,
+                                  max_disp, Workspace::legacy(), stream);
 }
 
 int decnet_spamat_backward(const float *ref, const float *tar, const float *ref_mask,
@@ -215,13 +307,8 @@ int decnet_spamat_backward(const float *ref, const float *tar, const float *ref_
                            const float *sum_similarities, const float *max_cost,
                            const float *grad_output, float *grad_ref, float *grad_tar, int B, int C,
                            int H, int W, int max_disp, void *stream) {
-    const void *p[] = {ref, tar, ref_mask, tar_mask, output, sum_similarities, max_cost,
-                       grad_output, grad_ref, grad_tar};
-    int rc = decnet_check_spamat_args(p, 10, B, C, H, W, max_disp);
-    if (rc) return rc;
-    return backward_dispatch(0, ref, tar, ref_mask, tar_mask, nullptr, output,
-                                   sum_similarities, max_cost, grad_output, grad_ref, grad_tar,
-                                   nullptr, B, C, H, W, max_disp, (hipStream_t)stream);
+    return spamat_backward(ref, tar, ref_mask, tar_mask, output, sum_similarities, max_cost, grad_output, grad_ref,
+                           grad_tar, B, C, H, W, max_disp, Workspace::legacy(), stream);
 }
 
 int decnet_spavar_backward(const float *ref, const float *tar, const float *ref_mask,
@@ -230,13 +317,59 @@ int decnet_spavar_backward(const float *ref, const float *tar, const float *ref_
                            const float *grad_output, float *grad_ref, float *grad_tar,
                            float *grad_disparity, int B, int C, int H, int W, int max_disp,
                            void *stream) {
-    const void *p[] = {ref, tar, ref_mask, tar_mask, disparity, output, sum_similarities, max_cost,
-                       grad_output, grad_ref, grad_tar, grad_disparity};
-    int rc = decnet_check_spamat_args(p, 12, B, C, H, W, max_disp);
-    if (rc) return rc;
-    return backward_dispatch(1, ref, tar, ref_mask, tar_mask, disparity, output,
-                                   sum_similarities, max_cost, grad_output, grad_ref, grad_tar,
-                                   grad_disparity, B, C, H, W, max_disp, (hipStream_t)stream);
+    return spavar_backward(ref, tar, ref_mask, tar_mask, disparity, output, sum_similarities, max_cost, grad_output,
+                           grad_ref, grad_tar, grad_disparity, B, C, H, W, max_disp, Workspace::legacy(), stream);
+}
+
+size_t decnet_spamat_workspace_floats(int B, int C, int H, int W, int max_disp, int which) {
+    return workspace_floats(B, C, H, W, max_disp, which);
+}
+
+int decnet_spamat_forward_ws(const float *ref, const float *tar, const float *ref_mask, const float *tar_mask,
+                             float *output, float *sum_similarities, float *max_cost, int B, int C, int H, int W,
+                             int max_disp, float *workspace, size_t workspace_floats, void *stream) {
+    return spamat_forward(ref, tar, ref_mask, tar_mask, output, sum_similarities, max_cost, B, C, H, W, max_disp,
+                          Workspace{workspace, workspace_floats, true}, stream);
+}
+
+int decnet_spavar_forward_ws(const float *ref, const float *tar, const float *ref_mask, const float *tar_mask,
+                             const float *disparity, float *output, float *sum_similarities, float *max_cost, int B,
+                             int C, int H, int W, int max_disp, float *workspace, size_t workspace_floats, void *stream) {
+    return spavar_forward(ref, tar, ref_mask, tar_mask, disparity, output, sum_similarities, max_cost, B, C, H, W,
+                          max_disp, Workspace{workspace, workspace_floats, true}, stream);
+}
+
+int decnet_spamatvar_forward_ws(const float *ref, const float *tar, const float *ref_mask, const float *tar_mask,
+                                float *output, float *variance, float *sum_similarities, float *max_cost, int B, int C,
+                                int H, int W, int max_disp, float *workspace, size_t workspace_floats, void *stream) {
+    return spamatvar_forward(ref, tar, ref_mask, tar_mask, output, variance, sum_similarities, max_cost, B, C, H, W,
+                             max_disp, Workspace{workspace, workspace_floats, true}, stream);
+}
+
+int decnet_spamatvar_forward_bits_ws(const float *ref, const float *tar, const unsigned long long *ref_bits,
+                                     const unsigned long long *tar_bits, float *output, float *variance,
+                                     float *sum_similarities, float *max_cost, int B, int C, int H, int W, int max_disp,
+                                     float *workspace, size_t workspace_floats, void *stream) {
+    return spamatvar_forward_bits(ref, tar, ref_bits, tar_bits, output, variance, sum_similarities, max_cost, B, C, H, W,
+                                  max_disp, Workspace{workspace, workspace_floats, true}, stream);
+}
+
+int decnet_spamat_backward_ws(const float *ref, const float *tar, const float *ref_mask, const float *tar_mask,
+                              const float *output, const float *sum_similarities, const float *max_cost,
+                              const float *grad_output, float *grad_ref, float *grad_tar, int B, int C, int H, int W,
+                              int max_disp, float *workspace, size_t workspace_floats, void *stream) {
+    return spamat_backward(ref, tar, ref_mask, tar_mask, output, sum_similarities, max_cost, grad_output, grad_ref,
+                           grad_tar, B, C, H, W, max_disp, Workspace{workspace, workspace_floats, true}, stream);
+}
+
+int decnet_spavar_backward_ws(const float *ref, const float *tar, const float *ref_mask, const float *tar_mask,
+                              const float *disparity, const float *output, const float *sum_similarities,
+                              const float *max_cost, const float *grad_output, float *grad_ref, float *grad_tar,
+                              float *grad_disparity, int B, int C, int H, int W, int max_disp, float *workspace,
+                              size_t workspace_floats, void *stream) {
+    return spavar_backward(ref, tar, ref_mask, tar_mask, disparity, output, sum_similarities, max_cost, grad_output,
+                           grad_ref, grad_tar, grad_disparity, B, C, H, W, max_disp,
+                           Workspace{workspace, workspace_floats, true}, stream);
 }
 
 }  // extern "C"

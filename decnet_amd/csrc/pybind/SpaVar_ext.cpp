@@ -17,12 +17,14 @@ static int sparse_var_cuda_forward(at::Tensor ref_feas, at::Tensor tar_feas, at:
     db::check_plane(max_cost, "max_cost", ref_feas, d);
     TORCH_CHECK(max_disp >= 1, "max_disp must be >= 1, got ", max_disp);
     db::DeviceGuard guard(ref_feas.device());
-    const int rc = decnet_spavar_forward(ref_feas.data_ptr<float>(), tar_feas.data_ptr<float>(),
-                                         ref_mask.data_ptr<float>(), tar_mask.data_ptr<float>(),
-                                         disparity.data_ptr<float>(), output.data_ptr<float>(),
-                                         sum_similarities.data_ptr<float>(), max_cost.data_ptr<float>(), d.B, d.C,
-                                         d.H, d.W, max_disp, db::current_stream(ref_feas));
-    db::check_rc(rc, "decnet_spavar_forward");
+    const db::Workspace ws = db::workspace(ref_feas, d, max_disp, 1);
+    const int rc = decnet_spavar_forward_ws(ref_feas.data_ptr<float>(), tar_feas.data_ptr<float>(),
+                                            ref_mask.data_ptr<float>(), tar_mask.data_ptr<float>(),
+                                            disparity.data_ptr<float>(), output.data_ptr<float>(),
+                                            sum_similarities.data_ptr<float>(), max_cost.data_ptr<float>(), d.B, d.C,
+                                            d.H, d.W, max_disp, ws.p, ws.floats,
+                                            db::current_stream(ref_feas));
+    db::check_rc(rc, "decnet_spavar_forward_ws");
     return 1;
 }
 
@@ -44,14 +46,16 @@ static int sparse_var_cuda_backward(at::Tensor ref_feas, at::Tensor tar_feas, at
     db::check_plane(grad_disparity, "grad_disparity", ref_feas, d);
     TORCH_CHECK(max_disp >= 1, "max_disp must be >= 1, got ", max_disp);
     db::DeviceGuard guard(ref_feas.device());
-    const int rc = decnet_spavar_backward(ref_feas.data_ptr<float>(), tar_feas.data_ptr<float>(),
-                                          ref_mask.data_ptr<float>(), tar_mask.data_ptr<float>(),
-                                          disparity.data_ptr<float>(), output.data_ptr<float>(),
-                                          sum_similarities.data_ptr<float>(), max_cost.data_ptr<float>(),
-                                          grad_output.data_ptr<float>(), grad_ref_feas.data_ptr<float>(),
-                                          grad_tar_feas.data_ptr<float>(), grad_disparity.data_ptr<float>(), d.B,
-                                          d.C, d.H, d.W, max_disp, db::current_stream(ref_feas));
-    db::check_rc(rc, "decnet_spavar_backward");
+    const db::Workspace ws = db::workspace(ref_feas, d, max_disp, 5);
+    const int rc = decnet_spavar_backward_ws(ref_feas.data_ptr<float>(), tar_feas.data_ptr<float>(),
+                                             ref_mask.data_ptr<float>(), tar_mask.data_ptr<float>(),
+                                             disparity.data_ptr<float>(), output.data_ptr<float>(),
+                                             sum_similarities.data_ptr<float>(), max_cost.data_ptr<float>(),
+                                             grad_output.data_ptr<float>(), grad_ref_feas.data_ptr<float>(),
+                                             grad_tar_feas.data_ptr<float>(), grad_disparity.data_ptr<float>(), d.B,
+                                             d.C, d.H, d.W, max_disp, ws.p, ws.floats,
+                                             db::current_stream(ref_feas));
+    db::check_rc(rc, "decnet_spavar_backward_ws");
     return 1;
 }
 

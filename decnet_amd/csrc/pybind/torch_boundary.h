@@ -13,7 +13,9 @@
 //     of whatever it is given, SM_kernel.cu:369-376);
 //   * a device guard on ref_feas.device() and the CURRENT stream of that device (the reference launches on the
 //     legacy default stream and relies on the Python side's torch.cuda.device_of, functions/SpaMat.py:24);
-//   * a non-zero return code of the C ABI becomes a c10::Error (Python RuntimeError); the reference always returns 1.
+//   * a non-zero return code of the C ABI becomes a c10::Error (Python RuntimeError); the reference always returns 1;
+//   * disparity ranges wider than one band of the matrix-core kernels (max_disp > 273) go through the caller-workspace
+//     (`_ws`) entries on scratch from at::empty: the library owns no memory, and the call can be captured into a graph.
 #pragma once
 #include <torch/extension.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
@@ -67,5 +69,22 @@ inline void *current_stream(const at::Tensor &t) {
 }
 
 using DeviceGuard = c10::hip::HIPGuardMasqueradingAsCUDA;
+
+// Scratch of entry `which` of decnet_spamat_workspace_floats on ref's device; where the query is 0 (one band takes the
+// call) nothing is allocated and the `_ws` entry, given NULL, is the original entry.  Call under the device guard.
+struct Workspace {
+    at::Tensor t;
+    float *p = nullptr;
+    size_t floats = 0;
+};
+inline Workspace workspace(const at::Tensor &ref, const Dims &d, int max_disp, int which) {
+    Workspace w;
+    w.floats = decnet_spamat_workspace_floats(d.B, d.C, d.H, d.W, max_disp, which);
+    if (w.floats) {
+        w.t = at::empty({(int64_t)w.floats}, ref.options());           // float32 on ref's device, 16-byte aligned
+        w.p = w.t.data_ptr<float>();
+    }
+    return w;
+}
 
 }  // namespace decnet_boundary

@@ -13,9 +13,22 @@
 // (merge_band_fused).  A band without a
 // valid candidate comes back as m_b = 1e-6, S_b = 1e-6, out_b = 1 and contributes exactly nothing.  The backward kernels
 // take the GLOBAL max / sum / output (minus d0 where it is a disparity), write the band's gradients into scratch planes and
-// those are accumulated (the right gradient shifted back by d0).  Scratch comes from the stream-ordered allocator
-// (hipMallocAsync: (C + 8) planes forward, (3 C + 4) backward); while the stream is being captured the entry reports
-// DECNET_ERR_UNSUPPORTED and capi.hip falls back to the row-tile kernels.
+// those are accumulated (the right gradient shifted back by d0).
+//
+// Scratch: one sweep, two providers.  The `_ws` entries of include/decnet_hip.h hand in a caller workspace of
+// decnet_spamat_workspace_floats(...) floats (decnet_wide_workspace_floats below: a pure host function), and the sweep then
+// runs eagerly and under stream capture alike: no allocation, no synchronisation, no question about the stream.  The six
+// legacy entries pass no workspace: the same number of floats comes from the stream-ordered allocator (struct Scratch, the
+// only allocator calls of this file), and while the stream is being captured they report DECNET_ERR_UNSUPPORTED so that
+// capi.hip falls back to the row-tile kernels.
+//
+// Between band calls run two element-wise kernels, both row-structured (a wave owns a row: no division per element) with
+// 16-byte stores on the 16-byte-aligned middle of a row and scalar head / tail (rows of the reference's planes are not
+// multiples of four floats; the source, shifted by d0, is read in 16-byte units at 4-byte alignment):
+//   band_stage       one launch per band: the shifted right features, the shifted right mask (from the float plane, or
+//                    straight from the mask bits) and the offset disparity plane;
+//   band_accumulate  one launch per band of the backward: grad_ref += band, grad_tar += band shifted back, grad_disp += band.
+// Every element is one copy, one subtraction of d0 or one addition: the results do not depend on the launch shape.
 #include "common.h"
 
 int decnet_mfma_forward(int mode, const float *ref, const float *tar, const float *rmask, const float *tmask,
@@ -31,21 +44,107 @@ namespace {
 constexpr int WIDE_BAND = 272;          // widest band of the matrix-core kernels (18 tiles)
 constexpr int EW_THREADS = 256;
 
-// dst[p][y][x] = x >= d0 ? src[p][y][x - d0] : 0   over `planes` planes of H x W (features: B*C planes, masks: B)
-__global__ __launch_bounds__(EW_THREADS) void shift_planes(const float *__restrict__ src, float *__restrict__ dst,
-                                                           size_t rows, int W, int d0) {
-    const size_t n = rows * (size_t)W;
-    for (size_t i = (size_t)blockIdx.x * EW_THREADS + threadIdx.x; i < n; i += (size_t)gridDim.x * EW_THREADS) {
-        const int x = (int)(i % W);
-        dst[i] = x >= d0 ? src[i - d0] : 0.f;
+constexpr int ROW_WAVES = EW_THREADS / DECNET_WAVE;      // rows a workgroup works on at a time (one per wave)
+
+// ---- row jobs: `rows` rows of W floats, dst row r made from src row r ----------------------------------------------
+enum RowKind {
+    ROW_SHIFT = 0,      // dst[x] = x >= shift ? src[x - shift] : 0                                (right features / mask)
+    ROW_BITS = 1,       // the same from a bit-packed mask row (wpr 64-bit words, bit i of word w = pixel 64 w + i)
+    ROW_OFFSET = 2,     // dst[x] = src[x] - off                                                   (the band's disparity plane)
+    ROW_ADD = 3,        // dst[x] += src[x + shift] for x + shift < W                              (gradient accumulation)
+};
+struct RowJob {
+    const void *src;
+    float *dst;
+    unsigned rows;      // 0: unused slot
+    int kind, shift;
+    float off;
+};
+struct RowJobs { RowJob j[3]; };
+
+typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));       // 16-byte access at 4-byte alignment (source rows)
+typedef float f4a __attribute__((ext_vector_type(4), aligned(16)));      // ... at 16-byte alignment (destination rows)
+
+template <int KIND>
+__device__ __forceinline__ float row_elem(const float *__restrict__ s, const unsigned long long *__restrict__ w,
+                                          const float *d, int x, int shift, float off) {
+    if (KIND == ROW_SHIFT) return x >= shift ? s[x - shift] : 0.f;
+    if (KIND == ROW_BITS) return x >= shift ? (float)((w[(x - shift) >> 6] >> ((x - shift) & 63)) & 1ull) : 0.f;
+    if (KIND == ROW_OFFSET) return s[x] - off;
+    return d[x] + s[x + shift];
+}
+
+// One row by one wave.  s / w: the source row (floats / mask words), d: the destination row.  Elements [0, xe) are written,
+// xe = W (ROW_ADD: W - shift: the source row ends there); every source index stays inside the row: [0, W - shift) for the
+// shifts, [shift, W) for ROW_ADD.
+template <int KIND>
+__device__ __forceinline__ void wave_row(const float *__restrict__ s, const unsigned long long *__restrict__ w, float *d,
+                                         int W, int shift, float off, int lane) {
+    const int xe = KIND == ROW_ADD ? W - shift : W;
+    if (xe <= 0) return;
+    int head = (int)((4u - (unsigned)(((uintptr_t)d >> 2) & 3u)) & 3u);  // elements before the first 16-byte boundary of d
+    if (head > xe) head = xe;
+    const int nv = (xe - head) >> 2;
+    if (lane < head) d[lane] = row_elem<KIND>(s, w, d, lane, shift, off);
+    for (int v = lane; v < nv; v += DECNET_WAVE) {
+        const int x = head + 4 * v;
+        f4a o;
+        if (KIND == ROW_SHIFT && x >= shift) {
+            const f4u a = *reinterpret_cast<const f4u *>(s + (x - shift));
+            o = {a.x, a.y, a.z, a.w};
+        } else if (KIND == ROW_BITS && x >= shift && ((x - shift) & 63) <= 60) {
+            const unsigned long long bits = w[(x - shift) >> 6] >> ((x - shift) & 63);
+            o = {(float)(bits & 1ull), (float)((bits >> 1) & 1ull), (float)((bits >> 2) & 1ull), (float)((bits >> 3) & 1ull)};
+        } else if (KIND == ROW_OFFSET) {
+            const f4u a = *reinterpret_cast<const f4u *>(s + x);
+            o = {a.x - off, a.y - off, a.z - off, a.w - off};
+        } else if (KIND == ROW_ADD) {
+            const f4u a = *reinterpret_cast<const f4u *>(s + (x + shift));
+            const f4a c = *reinterpret_cast<const f4a *>(d + x);
+            o = {c.x + a.x, c.y + a.y, c.z + a.z, c.w + a.w};
+        } else {                                                          // a shift's vector that straddles x = shift, or lies left of it
+            o = {row_elem<KIND>(s, w, d, x, shift, off), row_elem<KIND>(s, w, d, x + 1, shift, off),
+                 row_elem<KIND>(s, w, d, x + 2, shift, off), row_elem<KIND>(s, w, d, x + 3, shift, off)};
+        }
+        *reinterpret_cast<f4a *>(d + x) = o;
+    }
+    const int x = head + 4 * nv + lane;
+    if (x < xe) d[x] = row_elem<KIND>(s, w, d, x, shift, off);
+}
+
+// the rows of up to three jobs, dealt to the waves of the grid; which job a row belongs to is decided once per row
+__device__ __forceinline__ void run_row_jobs(const RowJobs &jobs, int W, int wpr) {
+    const int lane = threadIdx.x & (DECNET_WAVE - 1), wave = threadIdx.x / DECNET_WAVE;
+    const size_t r0 = jobs.j[0].rows, r1 = r0 + jobs.j[1].rows, total = r1 + jobs.j[2].rows;
+    for (size_t r = (size_t)blockIdx.x * ROW_WAVES + wave; r < total; r += (size_t)gridDim.x * ROW_WAVES) {
+        const int k = r < r0 ? 0 : r < r1 ? 1 : 2;
+        const size_t q = k == 0 ? r : k == 1 ? r - r0 : r - r1;
+        const void *src = k == 0 ? jobs.j[0].src : k == 1 ? jobs.j[1].src : jobs.j[2].src;
+        float *dst = (k == 0 ? jobs.j[0].dst : k == 1 ? jobs.j[1].dst : jobs.j[2].dst) + q * W;
+        const int kind = k == 0 ? jobs.j[0].kind : k == 1 ? jobs.j[1].kind : jobs.j[2].kind;
+        const int shift = k == 0 ? jobs.j[0].shift : k == 1 ? jobs.j[1].shift : jobs.j[2].shift;
+        const float off = k == 0 ? jobs.j[0].off : k == 1 ? jobs.j[1].off : jobs.j[2].off;
+        const float *s = static_cast<const float *>(src) + q * W;
+        const unsigned long long *w = static_cast<const unsigned long long *>(src) + q * wpr;
+        if (kind == ROW_SHIFT) wave_row<ROW_SHIFT>(s, nullptr, dst, W, shift, off, lane);
+        else if (kind == ROW_BITS) wave_row<ROW_BITS>(nullptr, w, dst, W, shift, off, lane);
+        else if (kind == ROW_OFFSET) wave_row<ROW_OFFSET>(s, nullptr, dst, W, shift, off, lane);
+        else wave_row<ROW_ADD>(s, nullptr, dst, W, shift, off, lane);
     }
 }
-// dst = src - d0 (the disparity-like input of a band)
-__global__ __launch_bounds__(EW_THREADS) void offset_plane(const float *__restrict__ src, float *__restrict__ dst, size_t n,
-                                                           float d0) {
-    for (size_t i = (size_t)blockIdx.x * EW_THREADS + threadIdx.x; i < n; i += (size_t)gridDim.x * EW_THREADS)
-        dst[i] = src[i] - d0;
+// what a band call reads: the right features and the right mask shifted by d0, the disparity-like plane minus d0
+__global__ __launch_bounds__(EW_THREADS) void band_stage(RowJobs jobs, int W, int wpr) { run_row_jobs(jobs, W, wpr); }
+// what a band call of the backward wrote, added to the running gradients (ROW_ADD jobs only)
+__global__ __launch_bounds__(EW_THREADS) void band_accumulate(RowJobs jobs, int W) { run_row_jobs(jobs, W, 0); }
+
+inline RowJob row_job(int kind, const void *src, float *dst, size_t rows, int shift, float off = 0.f) {
+    return RowJob{src, dst, (unsigned)rows, kind, shift, off};
 }
+inline unsigned row_grid(const RowJobs &jobs) {
+    const size_t rows = (size_t)jobs.j[0].rows + jobs.j[1].rows + jobs.j[2].rows, b = (rows + ROW_WAVES - 1) / ROW_WAVES;
+    return (unsigned)(b < 8192 ? (b ? b : 1) : 8192);
+}
+
 // running (q, S, m) <- merge with band (q_b, S_b, m_b); q is a quotient (1e-6 + Q) / S; d0f shifts the band's first moment
 // (disparity: d0; variance: 0).  Pixels with the left mask off keep their zeros.
 __global__ __launch_bounds__(EW_THREADS) void merge_band(const float *__restrict__ rmask, float *__restrict__ q,
@@ -93,27 +192,6 @@ __global__ __launch_bounds__(EW_THREADS) void merge_band_fused(const float *__re
         m[i] = mn;
     }
 }
-// acc += add (planes of W-wide rows); add is read shifted right by d0: acc[x] += add[x + d0] for x + d0 < W
-__global__ __launch_bounds__(EW_THREADS) void accumulate_planes(float *__restrict__ acc, const float *__restrict__ add,
-                                                                size_t rows, int W, int d0) {
-    const size_t n = rows * (size_t)W;
-    for (size_t i = (size_t)blockIdx.x * EW_THREADS + threadIdx.x; i < n; i += (size_t)gridDim.x * EW_THREADS) {
-        const int x = (int)(i % W);
-        if (x + d0 < W) acc[i] += add[i + d0];
-    }
-}
-// bit-packed masks [rows][ceil(W/64)] (bit i of word w = pixel 64 w + i) -> float planes
-__global__ __launch_bounds__(EW_THREADS) void unpack_bits(const unsigned long long *__restrict__ bits, float *__restrict__ dst,
-                                                          size_t rows, int W) {
-    const size_t n = rows * (size_t)W;
-    const int wpr = (W + 63) >> 6;
-    for (size_t i = (size_t)blockIdx.x * EW_THREADS + threadIdx.x; i < n; i += (size_t)gridDim.x * EW_THREADS) {
-        const size_t r = i / W;
-        const int x = (int)(i - r * W);
-        dst[i] = (float)((bits[r * wpr + (x >> 6)] >> (x & 63)) & 1ull);
-    }
-}
-
 inline unsigned ew_grid(size_t n) {
     const size_t b = (n + EW_THREADS - 1) / EW_THREADS;
     return (unsigned)(b < 8192 ? (b ? b : 1) : 8192);
@@ -126,13 +204,23 @@ inline bool capturing(hipStream_t stream) {
     }
     return cap != hipStreamCaptureStatusNone;
 }
-struct Scratch {                        // one stream-ordered allocation, freed (stream-ordered) when the call returns
+// Where a sweep's scratch comes from: the caller's workspace (the `_ws` entries), or -- ws == nullptr, the legacy entries -- one
+// stream-ordered allocation that is freed (stream-ordered) when the call returns.
+struct Scratch {
     float *p = nullptr;
+    bool own = false;
     hipStream_t s;
     explicit Scratch(hipStream_t st) : s(st) {}
-    int get(size_t floats) { return (int)hipMallocAsync((void **)&p, floats * sizeof(float), s); }
+    int get(float *ws, size_t floats) {
+        if (ws) {
+            p = ws;
+            return 0;
+        }
+        own = true;
+        return (int)hipMallocAsync((void **)&p, floats * sizeof(float), s);
+    }
     ~Scratch() {
-        if (p) (void)hipFreeAsync(p, s);
+        if (own && p) (void)hipFreeAsync(p, s);
     }
 };
 #define CK(expr)                              \
@@ -142,30 +230,57 @@ struct Scratch {                        // one stream-ordered allocation, freed 
     } while (0)
 #define LAUNCH_OK() CK(decnet_launch_status())
 
+// planes of np = B H W floats a forward sweep needs: the shifted right features (C), the shifted right mask, the band's
+// (q, S, m); + the offset disparity (SpaVar) / the band's variance (fused); + the unpacked left mask (bit-mask entry)
+inline size_t forward_planes(int C, int mode, int mbits) { return (size_t)C + 4 + (mode ? 1 : 0) + (mbits ? 1 : 0); }
+// ... and a backward sweep: the shifted right features and the band's two feature gradients (3 C), the shifted right mask,
+// the offset disparity-like plane; + the band's grad_disparity (SpaVar)
+inline size_t backward_planes(int C, int var) { return 3 * (size_t)C + 2 + (var ? 1 : 0); }
+
 }  // namespace
 
+// decnet_spamat_workspace_floats of include/decnet_hip.h for valid dims (capi.hip checks them): 0 where one band takes the
+// call.  which: 0 spamat_forward, 1 spavar_forward, 2 spamatvar_forward, 3 spamatvar_forward_bits, 4 spamat_backward,
+// 5 spavar_backward.  No HIP call.
+size_t decnet_wide_workspace_floats(int B, int C, int H, int W, int D, int which) {
+    if (D <= WIDE_BAND + 1 || which < 0 || which > 5) return 0;
+    const size_t np = (size_t)B * H * W;
+    if (which >= 4) return backward_planes(C, which == 5) * np;
+    return forward_planes(C, which == 3 ? 2 : which, which == 3) * np;
+}
+
 // mode 0 SpaMat (out, S, m), 1 SpaVar (var_out, S, m; `disparity` given), 2 fused (out, var_out, S, m).
-// mbits: the masks are bit-packed (decnet_spamatvar_forward_bits): unpacked into scratch planes first.
+// mbits: the masks are bit-packed (decnet_spamatvar_forward_bits): the left mask is unpacked into a scratch plane once, the
+// right mask per band straight into its shifted form.
+// ws: the caller's workspace (decnet_wide_workspace_floats floats, checked by capi.hip), or nullptr: allocate, and decline
+// while the stream is being captured.
 int decnet_wide_forward(int mode, const float *ref, const float *tar, const float *rmask, const float *tmask,
                         const float *disparity, float *out, float *var_out, float *sum_sim, float *max_cost, int B, int C,
-                        int H, int W, int D, int allow_compact, int mbits, hipStream_t stream) {
+                        int H, int W, int D, int allow_compact, int mbits, float *ws, hipStream_t stream) {
     if (D <= WIDE_BAND) return DECNET_ERR_UNSUPPORTED;
-    if (capturing(stream)) return DECNET_ERR_UNSUPPORTED;
-    const int nb = ceil_div(D, WIDE_BAND), Db = ceil_div(D, nb);
+    if (!ws && capturing(stream)) return DECNET_ERR_UNSUPPORTED;
+    const int nb = ceil_div(D, WIDE_BAND), Db = ceil_div(D, nb), wpr = (W + 63) >> 6;
     const size_t np = (size_t)B * H * W, rowsF = (size_t)B * C * H, rowsM = (size_t)B * H;
     Scratch sc(stream);
-    CK(sc.get((size_t)(C + 8) * np + 2 * np));
+    CK(sc.get(ws, forward_planes(C, mode, mbits) * np));
     float *Rb = sc.p, *tmb = Rb + (size_t)C * np, *qb = tmb + np, *Sb = qb + np, *mb = Sb + np, *db = mb + np,
-          *S2 = db + np, *m2 = S2 + np, *rmf = m2 + np, *tmf = rmf + np;
-    if (mbits) {
-        hipLaunchKernelGGL(unpack_bits, dim3(ew_grid(np)), dim3(EW_THREADS), 0, stream,
-                           reinterpret_cast<const unsigned long long *>(rmask), rmf, rowsM, W);
-        hipLaunchKernelGGL(unpack_bits, dim3(ew_grid(np)), dim3(EW_THREADS), 0, stream,
-                           reinterpret_cast<const unsigned long long *>(tmask), tmf, rowsM, W);
+          *rmf = db + (mode ? np : 0);                                  // db: modes 1, 2 only; rmf: mbits only
+    const void *tsrc = tmask;                                           // the right mask as the caller gave it
+    const int tkind = mbits ? ROW_BITS : ROW_SHIFT;
+    if (mbits) {                                                        // band 0 reads float planes like every other band
+        const RowJobs jobs = {{row_job(ROW_BITS, rmask, rmf, rowsM, 0), row_job(ROW_BITS, tmask, tmb, rowsM, 0), RowJob{}}};
+        hipLaunchKernelGGL(band_stage, dim3(row_grid(jobs)), dim3(EW_THREADS), 0, stream, jobs, W, wpr);
         LAUNCH_OK();
         rmask = rmf;
-        tmask = tmf;
+        tmask = tmb;
     }
+    // band b > 0 of a sweep: (Rb, tmb[, db = disp - d0]) in one launch
+    auto stage = [&](int d0, const float *disp) -> int {
+        const RowJobs jobs = {{row_job(ROW_SHIFT, tar, Rb, rowsF, d0), row_job(tkind, tsrc, tmb, rowsM, d0),
+                               disp ? row_job(ROW_OFFSET, disp, db, rowsM, 0, (float)d0) : RowJob{}}};
+        hipLaunchKernelGGL(band_stage, dim3(row_grid(jobs)), dim3(EW_THREADS), 0, stream, jobs, W, wpr);
+        return decnet_launch_status();
+    };
     // one sweep over the bands for a quotient q in {disparity (SpaMat), variance (SpaVar)}: band 0 lands in (q, S, m)
     // itself, the others in (qb, Sb, mb) and are merged in
     auto sweep = [&](int var, const float *disp, float *q, float *S, float *m) -> int {
@@ -173,11 +288,7 @@ int decnet_wide_forward(int mode, const float *ref, const float *tar, const floa
             const int d0 = b * Db, dw = (D - d0 < Db) ? D - d0 : Db;
             const float *Rv = tar, *tv = tmask, *dv = disp;
             if (b) {
-                hipLaunchKernelGGL(shift_planes, dim3(ew_grid(rowsF * W)), dim3(EW_THREADS), 0, stream, tar, Rb, rowsF, W, d0);
-                hipLaunchKernelGGL(shift_planes, dim3(ew_grid(np)), dim3(EW_THREADS), 0, stream, tmask, tmb, rowsM, W, d0);
-                if (var)
-                    hipLaunchKernelGGL(offset_plane, dim3(ew_grid(np)), dim3(EW_THREADS), 0, stream, disp, db, np, (float)d0);
-                LAUNCH_OK();
+                CK(stage(d0, var ? disp : nullptr));
                 Rv = Rb; tv = tmb; dv = db;
             }
             float *qo = b ? qb : q, *So = b ? Sb : S, *mo = b ? mb : m;
@@ -193,8 +304,7 @@ int decnet_wide_forward(int mode, const float *ref, const float *tar, const floa
     };
     if (mode == 1) return sweep(1, disparity, var_out, sum_sim, max_cost);
     if (mode == 0) return sweep(0, nullptr, out, sum_sim, max_cost);
-    // fused: one sweep of fused band calls (each band's variance around its own disparity), merged around the joint mean
-    (void)S2; (void)m2;
+    // fused: one sweep of fused band calls (each band's variance around its own disparity, in db), merged around the joint mean
     for (int b = 0; b < nb; ++b) {
         const int d0 = b * Db, dw = (D - d0 < Db) ? D - d0 : Db;
         if (!b) {
@@ -202,9 +312,7 @@ int decnet_wide_forward(int mode, const float *ref, const float *tar, const floa
                                    allow_compact, 0, stream));
             continue;
         }
-        hipLaunchKernelGGL(shift_planes, dim3(ew_grid(rowsF * W)), dim3(EW_THREADS), 0, stream, tar, Rb, rowsF, W, d0);
-        hipLaunchKernelGGL(shift_planes, dim3(ew_grid(np)), dim3(EW_THREADS), 0, stream, tmask, tmb, rowsM, W, d0);
-        LAUNCH_OK();
+        CK(stage(d0, nullptr));
         CK(decnet_mfma_forward(2, ref, Rb, rmask, tmb, nullptr, qb, db, Sb, mb, B, C, H, W, dw, allow_compact, 0, stream));
         hipLaunchKernelGGL(merge_band_fused, dim3(ew_grid(np)), dim3(EW_THREADS), 0, stream, rmask, out, var_out, sum_sim,
                            max_cost, qb, db, Sb, mb, np, (float)d0);
@@ -213,18 +321,18 @@ int decnet_wide_forward(int mode, const float *ref, const float *tar, const floa
     return 0;
 }
 
-// var: 0 SpaMat, 1 SpaVar (also grad_disp).
+// var: 0 SpaMat, 1 SpaVar (also grad_disp).  ws as in decnet_wide_forward.
 int decnet_wide_backward(int var, const float *ref, const float *tar, const float *rmask, const float *tmask,
                          const float *disparity, const float *out, const float *sum_sim, const float *max_cost,
                          const float *grad_out, float *grad_ref, float *grad_tar, float *grad_disp, int B, int C, int H,
-                         int W, int D, hipStream_t stream) {
+                         int W, int D, float *ws, hipStream_t stream) {
     if (D <= WIDE_BAND) return DECNET_ERR_UNSUPPORTED;
-    if (capturing(stream)) return DECNET_ERR_UNSUPPORTED;
+    if (!ws && capturing(stream)) return DECNET_ERR_UNSUPPORTED;
     const int nb = ceil_div(D, WIDE_BAND), Db = ceil_div(D, nb);
     const size_t np = (size_t)B * H * W, nf = (size_t)C * np, rowsF = (size_t)B * C * H, rowsM = (size_t)B * H;
     Scratch sc(stream);
-    CK(sc.get(3 * nf + 3 * np));
-    float *Rb = sc.p, *glb = Rb + nf, *grb = glb + nf, *tmb = grb + nf, *sh = tmb + np, *gdb = sh + np;
+    CK(sc.get(ws, backward_planes(C, var) * np));
+    float *Rb = sc.p, *glb = Rb + nf, *grb = glb + nf, *tmb = grb + nf, *sh = tmb + np, *gdb = sh + np;   // gdb: SpaVar only
     for (int b = 0; b < nb; ++b) {
         const int d0 = b * Db, dw = (D - d0 < Db) ? D - d0 : Db;
         if (!b) {
@@ -232,16 +340,16 @@ int decnet_wide_backward(int var, const float *ref, const float *tar, const floa
                                     grad_disp, B, C, H, W, dw, stream));
             continue;
         }
-        hipLaunchKernelGGL(shift_planes, dim3(ew_grid(rowsF * W)), dim3(EW_THREADS), 0, stream, tar, Rb, rowsF, W, d0);
-        hipLaunchKernelGGL(shift_planes, dim3(ew_grid(np)), dim3(EW_THREADS), 0, stream, tmask, tmb, rowsM, W, d0);
         // the plane that is a disparity moves with the band: SpaMat's output (SM_kernel.cu:191), SpaVar's input (SV_kernel.cu:191)
-        hipLaunchKernelGGL(offset_plane, dim3(ew_grid(np)), dim3(EW_THREADS), 0, stream, var ? disparity : out, sh, np, (float)d0);
+        const RowJobs in = {{row_job(ROW_SHIFT, tar, Rb, rowsF, d0), row_job(ROW_SHIFT, tmask, tmb, rowsM, d0),
+                             row_job(ROW_OFFSET, var ? disparity : out, sh, rowsM, 0, (float)d0)}};
+        hipLaunchKernelGGL(band_stage, dim3(row_grid(in)), dim3(EW_THREADS), 0, stream, in, W, 0);
         LAUNCH_OK();
         CK(decnet_mfma_backward(var, ref, Rb, rmask, tmb, var ? sh : nullptr, var ? out : sh, sum_sim, max_cost, grad_out, glb, grb,
                                 var ? gdb : nullptr, B, C, H, W, dw, stream));
-        hipLaunchKernelGGL(accumulate_planes, dim3(ew_grid(nf)), dim3(EW_THREADS), 0, stream, grad_ref, glb, rowsF, W, 0);
-        hipLaunchKernelGGL(accumulate_planes, dim3(ew_grid(nf)), dim3(EW_THREADS), 0, stream, grad_tar, grb, rowsF, W, d0);
-        if (var) hipLaunchKernelGGL(accumulate_planes, dim3(ew_grid(np)), dim3(EW_THREADS), 0, stream, grad_disp, gdb, rowsM, W, 0);
+        const RowJobs acc = {{row_job(ROW_ADD, glb, grad_ref, rowsF, 0), row_job(ROW_ADD, grb, grad_tar, rowsF, d0),
+                              var ? row_job(ROW_ADD, gdb, grad_disp, rowsM, 0) : RowJob{}}};
+        hipLaunchKernelGGL(band_accumulate, dim3(row_grid(acc)), dim3(EW_THREADS), 0, stream, acc, W);
         LAUNCH_OK();
     }
     return 0;

@@ -92,15 +92,47 @@ def _feat_args(ref, tar, rmask, tmask, max_disp):
     return B, C, H, W, D
 
 
+# ---- disparity ranges wider than one band of the matrix-core kernels (max_disp > 273) ------------------------------------
+# Above that the library sweeps the range band by band and needs scratch.  The wrappers below allocate it with torch.empty
+# and call the `_ws` entry (include/decnet_hip.h): the library then owns no memory, and an allocation made by torch is what
+# makes the call capturable (under torch.cuda.graph it comes from the graph's private pool).  Up to 273 the query is 0 and
+# the original entry is called as before, with no query at all (one ctypes call matters at the host-bound small stages).
+ONE_BAND = 273                      # decnet_spamat_workspace_floats is 0 up to here, whatever the other dims
+WS_SPAMAT_FWD, WS_SPAVAR_FWD, WS_FUSED_FWD, WS_FUSED_BITS_FWD, WS_SPAMAT_BWD, WS_SPAVAR_BWD = range(6)
+_WS_FLOATS = {}
+
+
+def workspace_floats(B, C, H, W, D, which):
+    """decnet_spamat_workspace_floats, cached per shape (a pure host function of its arguments)."""
+    if D <= ONE_BAND:
+        return 0
+    key = (B, C, H, W, D, which)
+    n = _WS_FLOATS.get(key)
+    if n is None:
+        n = _WS_FLOATS[key] = int(_fn("decnet_spamat_workspace_floats")(B, C, H, W, D, which))
+    return n
+
+
+def _call(name, which, like, dims, *ptrs):
+    """Entry `name` on like's device and current stream: the original entry where one band takes the call, else its
+    `_ws` twin on a workspace allocated here."""
+    n = workspace_floats(*dims, which)
+    with _on_device(like):
+        if n == 0:
+            rc = _fn(name)(*ptrs, *dims, _stream(like))
+        else:
+            ws = torch.empty(n, dtype=_F32, device=like.device)        # torch allocations are 16-byte aligned
+            rc = _fn(name + "_ws")(*ptrs, *dims, ws.data_ptr(), n, _stream(like))
+    _lib.check(rc, name if n == 0 else name + "_ws")
+
+
 def spamat_forward(ref, tar, rmask, tmask, output, sum_sim, max_cost, max_disp):
     B, C, H, W, D = _feat_args(ref, tar, rmask, tmask, max_disp)
     for n, t in (("output", output), ("sum_similarities", sum_sim), ("max_cost", max_cost)):
         _chk(n, t, (B, H, W))
-    with _on_device(ref):
-        rc = _fn("decnet_spamat_forward")(
-            ref.data_ptr(), tar.data_ptr(), rmask.data_ptr(), tmask.data_ptr(), output.data_ptr(),
-            sum_sim.data_ptr(), max_cost.data_ptr(), B, C, H, W, D, _stream(ref))
-    _lib.check(rc, "decnet_spamat_forward")
+    _call("decnet_spamat_forward", WS_SPAMAT_FWD, ref, (B, C, H, W, D),
+          ref.data_ptr(), tar.data_ptr(), rmask.data_ptr(), tmask.data_ptr(), output.data_ptr(),
+          sum_sim.data_ptr(), max_cost.data_ptr())
 
 
 def spamat_backward(ref, tar, rmask, tmask, output, sum_sim, max_cost, grad_out, grad_ref, grad_tar,
@@ -111,12 +143,10 @@ def spamat_backward(ref, tar, rmask, tmask, output, sum_sim, max_cost, grad_out,
         _chk(n, t, (B, H, W))
     _chk("grad_ref_feas", grad_ref, (B, C, H, W))
     _chk("grad_tar_feas", grad_tar, (B, C, H, W))
-    with _on_device(ref):
-        rc = _fn("decnet_spamat_backward")(
-            ref.data_ptr(), tar.data_ptr(), rmask.data_ptr(), tmask.data_ptr(), output.data_ptr(),
-            sum_sim.data_ptr(), max_cost.data_ptr(), grad_out.data_ptr(), grad_ref.data_ptr(),
-            grad_tar.data_ptr(), B, C, H, W, D, _stream(ref))
-    _lib.check(rc, "decnet_spamat_backward")
+    _call("decnet_spamat_backward", WS_SPAMAT_BWD, ref, (B, C, H, W, D),
+          ref.data_ptr(), tar.data_ptr(), rmask.data_ptr(), tmask.data_ptr(), output.data_ptr(),
+          sum_sim.data_ptr(), max_cost.data_ptr(), grad_out.data_ptr(), grad_ref.data_ptr(),
+          grad_tar.data_ptr())
 
 
 def spavar_forward(ref, tar, rmask, tmask, disparity, output, sum_sim, max_cost, max_disp):
@@ -124,12 +154,9 @@ def spavar_forward(ref, tar, rmask, tmask, disparity, output, sum_sim, max_cost,
     for n, t in (("disparity", disparity), ("output", output), ("sum_similarities", sum_sim),
                  ("max_cost", max_cost)):
         _chk(n, t, (B, H, W))
-    with _on_device(ref):
-        rc = _fn("decnet_spavar_forward")(
-            ref.data_ptr(), tar.data_ptr(), rmask.data_ptr(), tmask.data_ptr(),
-            disparity.data_ptr(), output.data_ptr(), sum_sim.data_ptr(), max_cost.data_ptr(),
-            B, C, H, W, D, _stream(ref))
-    _lib.check(rc, "decnet_spavar_forward")
+    _call("decnet_spavar_forward", WS_SPAVAR_FWD, ref, (B, C, H, W, D),
+          ref.data_ptr(), tar.data_ptr(), rmask.data_ptr(), tmask.data_ptr(),
+          disparity.data_ptr(), output.data_ptr(), sum_sim.data_ptr(), max_cost.data_ptr())
 
 
 def spavar_backward(ref, tar, rmask, tmask, disparity, output, sum_sim, max_cost, grad_out,
@@ -140,13 +167,10 @@ def spavar_backward(ref, tar, rmask, tmask, disparity, output, sum_sim, max_cost
         _chk(n, t, (B, H, W))
     _chk("grad_ref_feas", grad_ref, (B, C, H, W))
     _chk("grad_tar_feas", grad_tar, (B, C, H, W))
-    with _on_device(ref):
-        rc = _fn("decnet_spavar_backward")(
-            ref.data_ptr(), tar.data_ptr(), rmask.data_ptr(), tmask.data_ptr(),
-            disparity.data_ptr(), output.data_ptr(), sum_sim.data_ptr(), max_cost.data_ptr(),
-            grad_out.data_ptr(), grad_ref.data_ptr(), grad_tar.data_ptr(), grad_disp.data_ptr(),
-            B, C, H, W, D, _stream(ref))
-    _lib.check(rc, "decnet_spavar_backward")
+    _call("decnet_spavar_backward", WS_SPAVAR_BWD, ref, (B, C, H, W, D),
+          ref.data_ptr(), tar.data_ptr(), rmask.data_ptr(), tmask.data_ptr(),
+          disparity.data_ptr(), output.data_ptr(), sum_sim.data_ptr(), max_cost.data_ptr(),
+          grad_out.data_ptr(), grad_ref.data_ptr(), grad_tar.data_ptr(), grad_disp.data_ptr())
 
 
 def spamatvar_forward_bits(ref, tar, rbits, tbits, max_disp, out=None):
@@ -170,11 +194,9 @@ def spamatvar_forward_bits(ref, tar, rbits, tbits, max_disp, out=None):
     o, v, s, m = out
     for n, t in (("output", o), ("variance", v), ("sum_similarities", s), ("max_cost", m)):
         _chk(n, t, (B, H, W))
-    with _on_device(ref):
-        rc = _fn("decnet_spamatvar_forward_bits")(
-            ref.data_ptr(), tar.data_ptr(), rbits.data_ptr(), tbits.data_ptr(), o.data_ptr(),
-            v.data_ptr(), s.data_ptr(), m.data_ptr(), B, C, H, W, D, _stream(ref))
-    _lib.check(rc, "decnet_spamatvar_forward_bits")
+    _call("decnet_spamatvar_forward_bits", WS_FUSED_BITS_FWD, ref, (B, C, H, W, D),
+          ref.data_ptr(), tar.data_ptr(), rbits.data_ptr(), tbits.data_ptr(), o.data_ptr(),
+          v.data_ptr(), s.data_ptr(), m.data_ptr())
     return o, v, s, m
 
 
@@ -188,9 +210,7 @@ def spamatvar_forward(ref, tar, rmask, tmask, max_disp, out=None):
     o, v, s, m = out
     for n, t in (("output", o), ("variance", v), ("sum_similarities", s), ("max_cost", m)):
         _chk(n, t, (B, H, W))
-    with _on_device(ref):
-        rc = _fn("decnet_spamatvar_forward")(
-            ref.data_ptr(), tar.data_ptr(), rmask.data_ptr(), tmask.data_ptr(), o.data_ptr(),
-            v.data_ptr(), s.data_ptr(), m.data_ptr(), B, C, H, W, D, _stream(ref))
-    _lib.check(rc, "decnet_spamatvar_forward")
+    _call("decnet_spamatvar_forward", WS_FUSED_FWD, ref, (B, C, H, W, D),
+          ref.data_ptr(), tar.data_ptr(), rmask.data_ptr(), tmask.data_ptr(), o.data_ptr(),
+          v.data_ptr(), s.data_ptr(), m.data_ptr())
     return o, v, s, m

@@ -100,11 +100,61 @@ int decnet_spamatvar_forward(const float *ref, const float *tar, const float *re
  * of a row = pixel 64 w + i, zero past W (what decnet_detail_mask writes beside the float plane of the reference's
  * contract).  Same results as the float-mask call; 8 of the pass's 88 bytes per pixel (C = 8) are not read.
  * Above max_disp 273 (the 18 tiles of one band) the range is done in bands of <= 272 with the masks unpacked into scratch planes (stream-ordered
- * allocation); DECNET_ERR_UNSUPPORTED there only while `stream` is being captured into a graph. */
+ * allocation); DECNET_ERR_UNSUPPORTED there only while `stream` is being captured into a graph (this entry allocates; its
+ * caller-workspace twin decnet_spamatvar_forward_bits_ws below does not and runs under capture). */
 int decnet_spamatvar_forward_bits(const float *ref, const float *tar, const unsigned long long *ref_bits,
                                   const unsigned long long *tar_bits, float *output, float *variance,
                                   float *sum_similarities, float *max_cost, int B, int C, int H, int W,
                                   int max_disp, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * SpaMat / SpaVar with a caller workspace: the six entries above for disparity ranges wider than one band of the
+ * matrix-core kernels (max_disp > 273; the reference's demo data runs stage 3 at 405 and 621, demo.py:149-155), without
+ * memory of the library's own.  Above 273 candidates the range is swept in nb = ceil(max_disp / 272) bands of
+ * ceil(max_disp / nb) candidates, merged per pixel.  The six entries above take that sweep's scratch from the
+ * stream-ordered allocator and therefore decline while `stream` is being captured into a graph (the float-mask entries
+ * then run the row-tile kernels, the bit-mask entry returns DECNET_ERR_UNSUPPORTED); the `_ws` entries take it from the
+ * caller, never ask whether the stream is capturing, and reach no allocation, synchronisation or host read-back on that
+ * path (DECNET_CHECK_FINITE=1 keeps its own, and stays skipped under capture).
+ *   decnet_spamat_workspace_floats(B, C, H, W, max_disp, which)
+ *       which: 0 spamat_forward, 1 spavar_forward, 2 spamatvar_forward, 3 spamatvar_forward_bits, 4 spamat_backward,
+ *              5 spavar_backward
+ *       A pure host function (no HIP call).  0 for every shape one band takes (max_disp <= 273), for bad shapes and for
+ *       an unknown `which`; otherwise the floats the sweep of that entry needs, in planes of B H W floats:
+ *       C + 4 (which 0), C + 5 (1, 2), C + 6 (3: the unpacked left mask), 3 C + 2 (4), 3 C + 3 (5).
+ *   workspace, workspace_floats   device scratch and its size in floats
+ *       query == 0: `workspace` may be NULL and the call IS the entry above (same dispatch, same results).
+ *       query  > 0: workspace == NULL -> DECNET_ERR_NULL_POINTER; workspace_floats < query -> DECNET_ERR_BAD_SHAPE;
+ *       workspace not 16-byte aligned -> DECNET_ERR_MISALIGNED; in all three nothing is launched and no output is
+ *       touched.  Nothing outside workspace[0 .. query) is written; its contents are garbage before and after a call.
+ * Everything else (arguments, dispatch, DECNET_SPAMAT_KERNEL, DECNET_CHECK_FINITE, return values) is that of the entry
+ * above; under DECNET_SPAMAT_KERNEL=rowtile the workspace is checked and then unused.  The band kernels, the band split
+ * and the merge order are the same, and no kernel has floating-point atomics: called eagerly, a `_ws` entry returns
+ * bit for bit what the entry above returns.
+ * ------------------------------------------------------------------------------------- */
+size_t decnet_spamat_workspace_floats(int B, int C, int H, int W, int max_disp, int which);
+int decnet_spamat_forward_ws(const float *ref, const float *tar, const float *ref_mask, const float *tar_mask,
+                             float *output, float *sum_similarities, float *max_cost, int B, int C, int H, int W,
+                             int max_disp, float *workspace, size_t workspace_floats, void *stream);
+int decnet_spamat_backward_ws(const float *ref, const float *tar, const float *ref_mask, const float *tar_mask,
+                              const float *output, const float *sum_similarities, const float *max_cost,
+                              const float *grad_output, float *grad_ref, float *grad_tar, int B, int C, int H, int W,
+                              int max_disp, float *workspace, size_t workspace_floats, void *stream);
+int decnet_spavar_forward_ws(const float *ref, const float *tar, const float *ref_mask, const float *tar_mask,
+                             const float *disparity, float *output, float *sum_similarities, float *max_cost, int B,
+                             int C, int H, int W, int max_disp, float *workspace, size_t workspace_floats, void *stream);
+int decnet_spavar_backward_ws(const float *ref, const float *tar, const float *ref_mask, const float *tar_mask,
+                              const float *disparity, const float *output, const float *sum_similarities,
+                              const float *max_cost, const float *grad_output, float *grad_ref, float *grad_tar,
+                              float *grad_disparity, int B, int C, int H, int W, int max_disp, float *workspace,
+                              size_t workspace_floats, void *stream);
+int decnet_spamatvar_forward_ws(const float *ref, const float *tar, const float *ref_mask, const float *tar_mask,
+                                float *output, float *variance, float *sum_similarities, float *max_cost, int B, int C,
+                                int H, int W, int max_disp, float *workspace, size_t workspace_floats, void *stream);
+int decnet_spamatvar_forward_bits_ws(const float *ref, const float *tar, const unsigned long long *ref_bits,
+                                     const unsigned long long *tar_bits, float *output, float *variance,
+                                     float *sum_similarities, float *max_cost, int B, int C, int H, int W, int max_disp,
+                                     float *workspace, size_t workspace_floats, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * Stage 0 (coarsest level): dense cost volume -> 3-D conv aggregation -> soft-argmax.
