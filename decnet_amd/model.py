@@ -22,7 +22,7 @@ import torch.nn.functional as F
 
 from ._lib import DecnetHipError, UNSUPPORTED
 from .ops import spamatvar_forward, spamatvar_forward_bits
-from .stage0 import CostRegNetNoDown, Stage0
+from .stage0 import CachesWeights, CostRegNetNoDown, Stage0, drop_weight_caches, source_hold, source_key  # noqa: F401
 
 
 # bench.py's end-to-end accounting: a list that every Unit launch appends (kernel family, algorithmic flops, algorithmic
@@ -49,9 +49,11 @@ def _tally(unit, kind, x):
                   "bytes": 4.0 * B * (cin * H * W + co * Ho * Wo)})
 
 
-class Unit(nn.Module):
+class Unit(CachesWeights, nn.Module):
     """conv / transposed conv -> optional BatchNorm2d -> optional ReLU; attributes ``conv`` and
     ``bn`` as in the reference's Conv2dUnit / Deconv2dUnit (submodule.py:15-87)."""
+    _CACHE_ATTRS = ("_fold", "_fold_key", "_fold_src", "_mfold", "_mfold_key", "_mfold_src",
+                    "_tfold", "_tfold_key", "_tfold_src")
 
     def __init__(self, cin, cout, k, stride=1, pad=0, dil=1, relu=True, bn=True, momentum=0.1,
                  transposed=False):
@@ -127,13 +129,18 @@ class Unit(nn.Module):
               c.padding == (c.dilation[0] * (k // 2),) * 2 and c.groups == 1 and c.padding_mode == "zeros")
         return "conv" if ok else None
 
+    def _sources(self):
+        c, bn = self.conv, self.bn
+        return [c.weight] + ([bn.weight, bn.bias, bn.running_mean, bn.running_var] if bn is not None else
+                             ([c.bias] if c.bias is not None else []))
+
     def _folded(self, neg_last=False):
-        """Per-channel scale / shift of the eval-mode BatchNorm (or 1 / bias), cached per weight version.
+        """Per-channel scale / shift of the eval-mode BatchNorm (or 1 / bias), cached per weight version (stage0.source_key:
+        a write through ``.data`` after the first forward needs ``drop_weight_caches``).
         neg_last: the weights of the last input channel negated (a caller that feeds -x passes x instead)."""
         c, bn = self.conv, self.bn
-        ts = [c.weight] + ([bn.weight, bn.bias, bn.running_mean, bn.running_var] if bn is not None else
-                           ([c.bias] if c.bias is not None else []))
-        key = tuple((t.data_ptr(), t._version) for t in ts) + (bool(neg_last),)
+        ts = self._sources()
+        key = source_key(ts, bn.eps if bn is not None else None, bool(neg_last))
         if getattr(self, "_fold_key", None) != key:
             with torch.no_grad():
                 co = c.out_channels
@@ -158,15 +165,15 @@ class Unit(nn.Module):
                                                            torch.cuda.current_stream(w.device).cuda_stream),
                                "decnet_conv2d_pack_weight")
                 self._fold = (wp, scale.contiguous(), shift.contiguous())
-            self._fold_key = key
+            self._fold_key, self._fold_src = key, source_hold(ts)
         return self._fold
 
     def _folded_mfma(self):
-        """Weights split into bf16 terms in the operand layout of csrc/conv2d_mfma.hip + folded BN, cached per version."""
+        """Weights split into bf16 terms in the operand layout of csrc/conv2d_mfma.hip + folded BN, cached per version
+        (stage0.source_key: a write through ``.data`` after the first forward needs ``drop_weight_caches``)."""
         c, bn = self.conv, self.bn
-        ts = [c.weight] + ([bn.weight, bn.bias, bn.running_mean, bn.running_var] if bn is not None else
-                           ([c.bias] if c.bias is not None else []))
-        key = tuple((t.data_ptr(), t._version) for t in ts)
+        ts = self._sources()
+        key = source_key(ts, bn.eps if bn is not None else None)
         if getattr(self, "_mfold_key", None) != key:
             from . import _lib
             L = _lib.lib()
@@ -196,7 +203,7 @@ class Unit(nn.Module):
                         _lib.check(L.decnet_conv2d_mfma_pack_weight(w.data_ptr(), wp.data_ptr(), ci, co, k, st),
                                    "decnet_conv2d_mfma_pack_weight")
                 self._mfold = (wp, scale.contiguous(), shift.contiguous())
-            self._mfold_key = key
+            self._mfold_key, self._mfold_src = key, source_hold(ts)
         return self._mfold
 
     def _forward_mfma(self, x):
@@ -331,17 +338,18 @@ class Unit(nn.Module):
 
     def _folded_torch(self):
         """Eval-mode BatchNorm folded into the convolution itself (w * scale per output channel, bias =
-        shift) for the layers that stay on MIOpen: one kernel instead of conv + batch-norm."""
+        shift) for the layers that stay on MIOpen: one kernel instead of conv + batch-norm.  Cached per version
+        (stage0.source_key: a write through ``.data`` after the first forward needs ``drop_weight_caches``)."""
         c, bn = self.conv, self.bn
-        key = tuple((t.data_ptr(), t._version) for t in (c.weight, bn.weight, bn.bias, bn.running_mean,
-                                                         bn.running_var))
+        ts = self._sources()
+        key = source_key(ts, bn.eps)
         if getattr(self, "_tfold_key", None) != key:
             with torch.no_grad():
                 scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)
                 shift = bn.bias - bn.running_mean * scale
                 shape = (1, -1, 1, 1) if isinstance(c, nn.ConvTranspose2d) else (-1, 1, 1, 1)
                 self._tfold = ((c.weight * scale.view(shape)).contiguous(), shift.contiguous())
-            self._tfold_key = key
+            self._tfold_key, self._tfold_src = key, source_hold(ts)
         return self._tfold
 
     def forward(self, x):
@@ -381,6 +389,9 @@ class Unit(nn.Module):
         return F.relu(x) if self.relu else x
 
 
+# masks_of(): both views' mask generators as one batch up to this many bytes of level features (see there)
+TWO_VIEW_MASK_BYTES = 96 << 20
+
 _SIDE = threading.local()
 
 
@@ -416,8 +427,9 @@ class UpBlock(nn.Module):
         return self.conv((up, skip)), up                # Unit takes the concatenation as a tuple
 
 
-class ASPP(nn.Module):
+class ASPP(CachesWeights, nn.Module):
     """submodule.py:225-241: a 1x1 branch and three dilated 3x3 branches, concatenated."""
+    _CACHE_ATTRS = ("_pk", "_pk_key", "_pk_src")
 
     def __init__(self, cin, cout, rates):
         super().__init__()
@@ -446,10 +458,12 @@ class ASPP(nn.Module):
         return True
 
     def _packed(self):
+        """All branches' weights in the per-tap GEMM's layout + folded BN, cached per version (stage0.source_key: a
+        write through ``.data`` after the first forward needs ``drop_weight_caches``)."""
         from . import _lib
         units = list(self.stages.children())
         ts = [t for u in units for t in (u.conv.weight, u.bn.weight, u.bn.bias, u.bn.running_mean, u.bn.running_var)]
-        key = tuple((t.data_ptr(), t._version) for t in ts)
+        key = source_key(ts, *[u.bn.eps for u in units])
         if getattr(self, "_pk_key", None) != key:
             L = _lib.lib()
             dev = units[0].conv.weight.device
@@ -472,7 +486,7 @@ class ASPP(nn.Module):
                 torch.cuda.current_stream(dev).synchronize()          # w temporaries may go now
             self._pk = dict(u=u_all, scale=torch.cat(scale).contiguous(), shift=torch.cat(shift).contiguous(),
                             ks=ks, tap0=tap0, ntaps=ntaps, dil=[u.conv.dilation[0] for u in units])
-            self._pk_key = key
+            self._pk_key, self._pk_src = key, source_hold(ts)
         return self._pk
 
     def _forward_hip(self, x):
@@ -556,9 +570,10 @@ class FeatExtNetChannelPlus(nn.Module):
         return {"stage0": f3, "stage1": s1, "stage2": s2, "stage3": s3}
 
 
-class GenerateSparseMask(nn.Module):
+class GenerateSparseMask(CachesWeights, nn.Module):
     """submodule.py:347-372: squared difference between the level's features and the upsampled
     previous level's, reduced to one logit per pixel."""
+    _CACHE_ATTRS = ("_hp", "_hp_key", "_hp_src")
 
     def __init__(self, in_channels, down_scale):
         super().__init__()
@@ -573,11 +588,12 @@ class GenerateSparseMask(nn.Module):
 
     def _host_params(self):
         """The 3x3 and 1x1 units of ``conv`` with BatchNorm folded, as host arrays (90 floats; one device ->
-        host copy per weight version)."""
+        host copy per weight version; stage0.source_key: a write through ``.data`` after the first forward needs
+        ``drop_weight_caches``)."""
         import ctypes
         u3, u1 = self.conv[0], self.conv[1]
         ts = [t for u in (u3, u1) for t in (u.conv.weight, u.bn.weight, u.bn.bias, u.bn.running_mean, u.bn.running_var)]
-        key = tuple((t.data_ptr(), t._version) for t in ts)
+        key = source_key(ts, u3.bn.eps, u1.bn.eps)
         if getattr(self, "_hp_key", None) != key:
             with torch.no_grad():
                 def fold(u):
@@ -589,7 +605,7 @@ class GenerateSparseMask(nn.Module):
                                   s1, b1]).cpu().tolist()
             arr = lambda v: (ctypes.c_float * len(v))(*v)
             self._hp = (arr(flat[0:81]), arr(flat[81:84]), arr(flat[84:87]), arr(flat[87:90]), flat[90], flat[91])
-            self._hp_key = key
+            self._hp_key, self._hp_src = key, source_hold(ts)
         return self._hp
 
     def mask(self, cur, pre, thold, want_bits=False):
@@ -787,6 +803,7 @@ class SparseDenseNetRefinementMask(nn.Module):
             elif isinstance(m, (nn.BatchNorm2d, nn.BatchNorm3d)):
                 m.weight.data.fill_(1)
                 m.bias.data.zero_()
+        drop_weight_caches(self)                        # the writes above go through .data: no cache key sees them
 
     def forward(self, left, right, disparity=None, left_mask_list=None, right_mask_list=None,
                 is_check=False, is_eval=False):
@@ -817,7 +834,7 @@ class SparseDenseNetRefinementMask(nn.Module):
             # both views as one batch of 2 B samples where the levels are launch-bound (1/9, 1/3 resolution); at full
             # resolution a [16,8,540,972] tensor is 268 MB -- more than the 256 MiB Infinity Cache that keeps a
             # view's 134 MB intermediates on chip between producer and consumer (measured: 656 vs 608 us)
-            if f2 is not None and 2 * L.numel() * 4 <= (96 << 20):
+            if f2 is not None and 2 * L.numel() * 4 <= TWO_VIEW_MASK_BYTES:
                 m2, b2 = gen.mask(f2["stage%d" % stage], f2["stage%d" % (stage - 1)], self.thold, want_bits=True)
                 nb = L.shape[0]
                 return m2[:nb], m2[nb:], (b2[:nb] if b2 is not None else None), (b2[nb:] if b2 is not None else None)

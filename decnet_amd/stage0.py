@@ -27,6 +27,57 @@ BN_EPS = 1e-5
 WINO_VARIANT = {"winograd": 0, "winograd4": 1, "winograd444": 2}
 
 
+def source_key(ts, *extra):
+    """Key of a packed-weight cache: (address, version) of every tensor it is built from, plus the plain values that go
+    into the packing.  It sees in-place writes under ``no_grad``, ``load_state_dict`` and a re-assigned ``.data`` at a new
+    address; it cannot see a write THROUGH ``.data`` (``p.data.copy_()``, ``p.data.normal_()``), which changes neither
+    -- such writes after the first forward need ``decnet_amd.drop_weight_caches(model)``."""
+    return tuple((t.data_ptr(), t._version) for t in ts) + tuple(extra)
+
+
+def source_hold(ts):
+    """Aliases of the tensors a cache entry was built from, kept beside the entry: an address that is still owned
+    cannot be handed out again by the caching allocator, so an equal key means the same memory (``p.data = other``
+    keeps ``_version``, ``load_state_dict(assign=True)`` resets it to 0)."""
+    return [t.detach() for t in ts]
+
+
+class CachesWeights:
+    """Mixin of the modules that keep packed weights / workspaces between calls.  The caches are derived data: they
+    are dropped when the parameters are moved or cast (``_apply``: ``.to()`` / ``.cpu()`` / ``.cuda()`` / ``.float()``)
+    or loaded (``load_state_dict``, both modes), and they take no part in ``copy.deepcopy`` / pickling (some hold
+    ctypes structures with pointers; a copy starts cold and repacks)."""
+    _CACHE_ATTRS = ()
+
+    def _drop_caches(self):
+        for a in self._CACHE_ATTRS:
+            self.__dict__.pop(a, None)
+
+    def __getstate__(self):
+        state = super().__getstate__()
+        for a in self._CACHE_ATTRS:
+            state.pop(a, None)
+        return state
+
+    def _apply(self, fn, *args, **kwargs):
+        self._drop_caches()
+        return super()._apply(fn, *args, **kwargs)
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        self._drop_caches()
+        return super()._load_from_state_dict(*args, **kwargs)
+
+
+def drop_weight_caches(module):
+    """Drop every packed-weight cache and workspace of ``module`` and its children; the next forward repacks from
+    the parameters as they are then.  Needed after a write through ``.data`` (see source_key).  HIP graphs captured
+    before the call point into the dropped buffers and must be captured again."""
+    for m in module.modules():
+        if isinstance(m, CachesWeights):
+            m._drop_caches()
+    return module
+
+
 def conv_algo(D=None):
     """The Conv3d algorithm of the 216-channel layers.  DECNET_CONV_ALGO = "winograd" (F(2,3) on D, H, W:
     3.4x fewer multiplications than the 27-tap sum), "winograd4" (F(2,3) on D, F(4,3) on H, W: 6x),
@@ -145,10 +196,11 @@ class Conv3dUnit(nn.Module):
         self.relu = relu
 
 
-class CostRegNetNoDown(nn.Module):
+class CostRegNetNoDown(CachesWeights, nn.Module):
     """forward: regularise the cost volume  (submodule.py:608-662)
     args:    x: cost volume, N*C*S*H*W
     return:  regularised cost volume, N*S*H*W"""
+    _CACHE_ATTRS = ("_packed", "_packed_key", "_packed_src", "_ws")
 
     def __init__(self, in_channels, base_channels, cost_func, down_scale=3):
         super(CostRegNetNoDown, self).__init__()
@@ -161,9 +213,18 @@ class CostRegNetNoDown(nn.Module):
                                    Conv3dUnit(C, C, padding=1))
         self.conv2 = nn.Sequential(Conv3dUnit(C, C, padding=1), Conv3dUnit(C, C, padding=1),
                                    Conv3dUnit(C, 1, padding=1, relu=False))
+        self._drop_caches()
+
+    def _drop_caches(self):
         self._packed = None
         self._packed_key = None
+        self._packed_src = None
         self._ws = {}
+
+    def __getstate__(self):
+        state = super().__getstate__()
+        state.update(_packed=None, _packed_key=None, _packed_src=None, _ws={})
+        return state
 
     def units(self):
         return list(self.conv0) + list(self.conv1) + list(self.conv2)
@@ -177,17 +238,20 @@ class CostRegNetNoDown(nn.Module):
         return r
 
     # ---- parameter preparation (once per weight version): repack + BN folding -----------
-    def _key(self):
-        k = [(self.conv_pre.weight.data_ptr(), self.conv_pre.weight._version)] if self.cost_func == "cat" else []
+    def _sources(self):
+        ts = [self.conv_pre.weight] if self.cost_func == "cat" else []
         for u in self.units():
-            for t in (u.conv.weight, u.bn.weight, u.bn.bias, u.bn.running_mean, u.bn.running_var):
-                k.append((t.data_ptr(), t._version))
-        return tuple(k)
+            ts += [u.conv.weight, u.bn.weight, u.bn.bias, u.bn.running_mean, u.bn.running_var]
+        return ts
+
+    def _key(self):
+        return source_key(self._sources(), *[(float(u.bn.eps), bool(u.relu)) for u in self.units()])
 
     def prepare(self, D=None):
         """Repack the 7 wide Conv3d weights to [27,Ci,CoP] on the device and fold eval-mode
         BatchNorm into per-channel scale/shift.  Cached until a parameter (or, through the choice
-        of algorithm, the depth D of the volume) changes."""
+        of algorithm, the depth D of the volume) changes.  The key is source_key's: a write through ``.data`` after
+        the first forward needs ``drop_weight_caches``."""
         algo = conv_algo(D)
         key = (algo,) + self._key()
         if self._packed is not None and key == self._packed_key:
@@ -254,7 +318,7 @@ class CostRegNetNoDown(nn.Module):
                 else:
                     wp = wpre
                 packed[0]["w_pre"], packed[0]["w_pre_true"] = wp, wpre
-        self._packed, self._packed_key = packed, key
+        self._packed, self._packed_key, self._packed_src = packed, key, source_hold(self._sources())
         return packed
 
     def _workspace(self, dev, n):

@@ -36,3 +36,36 @@ def spamat_spy(callback):
         yield
     finally:
         M.spamatvar_forward, M.spamatvar_forward_bits = orig_f, orig_b
+
+
+PLUMBING = ("_floats", "_bytes", "_pack_weight", "_split_weight", "decnet_conv3d_packed_cout", "decnet_version")
+
+
+@contextlib.contextmanager
+def entry_spy(plumbing=False):
+    """Record the names of the C entries (include/decnet_hip.h) the Python layer calls, in call order: yields the list.
+    The ctypes handle of decnet_amd._lib is replaced by a proxy for the duration (and the per-name lookups decnet_amd.ops
+    keeps are set aside).  plumbing=False leaves out size queries and weight packing, which depend on what is cached."""
+    from decnet_amd import _lib, ops
+    real = _lib.lib()
+    calls = []
+
+    class Proxy:
+        def __getattr__(self, name):
+            fn = getattr(real, name)
+            if not plumbing and (name.endswith(PLUMBING) or name in PLUMBING):
+                return fn
+
+            def call(*a):
+                calls.append(name)
+                return fn(*a)
+            return call
+    saved = dict(ops._FN)
+    ops._FN.clear()
+    _lib._lib = Proxy()
+    try:
+        yield calls
+    finally:
+        _lib._lib = real
+        ops._FN.clear()
+        ops._FN.update(saved)
