@@ -81,6 +81,9 @@ SIGNATURES = {
     "decnet_stage0_forward_cf": [_P] * 7 + [_I] * 7 + [_P],
     "decnet_ncdhw_to_ndhwc": [_P, _P] + [_I] * 5 + [_P],
     "decnet_ndhwc_to_ncdhw": [_P, _P] + [_I] * 5 + [_P],
+    "decnet_preprocess_u8": [_P] * 3 + [_I] * 5 + [_P],
+    "decnet_disparity_to_u16": [_P] * 2 + [_I] * 5 + [_P],
+    "decnet_disparity_metrics": [_P, _P, _F, _P] + [_I] * 5 + [_P],
 }
 
 

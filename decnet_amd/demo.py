@@ -86,6 +86,11 @@ def build_parser():
     p.add_argument("--root", default="./InputData/Sceneflow")
     p.add_argument("--resume", default=None)
     p.add_argument("--save2where", default="./Log/FirstTry")
+    p.add_argument("--pipeline", type=int, choices=(0, 1), default=0,
+                   help="1: decnet_amd.StereoEngine (uint8 upload, device pre/postprocessing, the forward as a HIP graph, "
+                        "copies overlapped); 0: one eager forward per pair")
+    p.add_argument("--batch_size", type=int, default=1, help="pairs per batch (--pipeline 1 only)")
+    p.add_argument("--workers", type=int, default=4, help="decoding threads (--pipeline 1 only; at most 16)")
     return p
 
 
@@ -135,6 +140,69 @@ def run_pair(model, left_img, right_img, device, n_disp=-1):
     return disparity_to_uint16(pred, ori_h, ori_w), dt
 
 
+def prefetched(pool, fn, items, ahead):
+    """``fn(item)`` for every item, in order, computed by ``pool`` at most ``ahead`` items ahead of the consumer (Executor.map
+    would start all of them at once and hold every decoded image until it is asked for)."""
+    import collections
+    pending = collections.deque()
+    for it in items:
+        pending.append(pool.submit(fn, it))
+        if len(pending) > ahead:
+            yield pending.popleft().result()
+    while pending:
+        yield pending.popleft().result()
+
+
+def pair_batches(items, batch_size):
+    """Consecutive runs of ``(name, left, right, n_disp)`` with one image size and one n_disp, cut at batch_size."""
+    batch = []
+    for it in items:
+        if batch and (len(batch) == batch_size or it[1].shape != batch[0][1].shape or it[2].shape != batch[0][2].shape
+                      or it[3] != batch[0][3]):
+            yield batch
+            batch = []
+        batch.append(it)
+    if batch:
+        yield batch
+
+
+def test_pipelined(args, model):
+    """--pipeline 1: pairs are read and decoded by a pool of host threads (host work only: every HIP call is made by this
+    thread), consecutive pairs of equal size and ndisp form a batch, PNGs are written as results arrive."""
+    from concurrent.futures import ThreadPoolExecutor
+    from .engine import StereoEngine
+    names = [n for n in sorted(os.listdir(args.root)) if os.path.isdir(os.path.join(args.root, n))]
+
+    def load(name):
+        d = os.path.join(args.root, name)
+        return (name, read_rgb(os.path.join(d, "im0.png")), read_rgb(os.path.join(d, "im1.png")),
+                read_ndisp(os.path.join(d, "calib.txt")))
+
+    def write(results):
+        for batch_names, disps, _ in results:
+            for name, img in zip(batch_names, disps):
+                write_png16(os.path.join(args.save2where, name + ".png"), img)
+
+    def with_range(items):
+        """n_disp -> the range the pair runs with: run_pair sets model.max_disp from a calib.txt and a pair without one
+        keeps what the pair before it ran with."""
+        cur = int(model.max_disp)
+        for name, left, right, n_disp in items:
+            cur = int(n_disp) if n_disp > 0 else cur
+            yield name, left, right, cur
+
+    engine = StereoEngine(model, batch_size=max(1, args.batch_size))
+    t0 = time.time()
+    workers = min(16, max(1, args.workers))
+    with ThreadPoolExecutor(max_workers=workers) as pool:
+        ahead = 2 * engine.batch_size + workers
+        for batch in pair_batches(with_range(prefetched(pool, load, names, ahead)), engine.batch_size):
+            engine.submit([b[1] for b in batch], [b[2] for b in batch], max_disp=batch[0][3], tag=[b[0] for b in batch])
+            write(engine.results())
+        write(engine.flush())
+    print("rebuild version, pipelined: {} pairs, cost time: {}".format(len(names), time.time() - t0))
+
+
 def test(args):
     torch.manual_seed(args.seed)
     if not torch.cuda.is_available():
@@ -142,6 +210,10 @@ def test(args):
     device = torch.device("cuda:0")
     os.makedirs(args.save2where, exist_ok=True)
     model = build_model(args, device)
+    if getattr(args, "pipeline", 0):
+        test_pipelined(args, model)
+        print("The testing is completed: {}".format(time.strftime("%Y-%m-%d %H:%M:%S", time.localtime(time.time()))))
+        return
     for name in sorted(os.listdir(args.root)):
         d = os.path.join(args.root, name)
         if not os.path.isdir(d):

@@ -23,7 +23,7 @@ import time
 import numpy as np
 import torch
 
-from .demo import disparity_to_uint16, write_png16
+from .demo import disparity_to_uint16, prefetched, write_png16
 from .dist import shard_range
 from .model import get_model, load_reference_checkpoint
 
@@ -69,6 +69,10 @@ def build_parser():
     p.add_argument("--resume", default=None)
     p.add_argument("--save2where", default="./Log/FirstTry")
     p.add_argument("--gpus", type=int, default=1, help="processes (one per GPU); > 1 without a launcher starts them")
+    p.add_argument("--pipeline", type=int, choices=(0, 1), default=0,
+                   help="1: decnet_amd.StereoEngine (uint8 upload, device pre/postprocessing and metrics, the forward as a "
+                        "HIP graph, copies overlapped); 0: one eager forward per batch")
+    p.add_argument("--workers", type=int, default=4, help="sample-loading threads (--pipeline 1 only; at most 16)")
     p.add_argument("--force-collective", action="store_true",
                    help="initialise RCCL and gather the metrics through it even with one rank (the N > 1 path on a "
                         "one-GPU box; same result)")
@@ -146,6 +150,9 @@ def test(args, model=None):
         torch.distributed.init_process_group("nccl", device_id=device)
     kind = get_loader(args.dataset)
     kw = dict(use_detail=bool(args.use_detail), max_disp=192)
+    pipeline = bool(getattr(args, "pipeline", 0))
+    if pipeline:
+        kw["raw"] = True
     dataset = kind(data_path(args), **kw) if args.dataset.lower() == "pairs" else \
         kind(data_path(args), split=args.test_split, **kw)
     if not args.is_eval and rank == 0:
@@ -154,29 +161,8 @@ def test(args, model=None):
         model = build_model(args, device)
     batches = batches_of(dataset, args.batch_size, args.dataset)
     lo, hi = shard_range(len(batches), rank, world)
-    rec = []                                                            # (batch index, epe, loss_3)
-    for bi in range(lo, hi):
-        (left, right, disparity, _image, lm1, lm2, lm3, rm1, rm2, rm3, ori_h, ori_w, names, n_disp) = collate(
-            [dataset[i] for i in batches[bi]])
-        with torch.no_grad():
-            model.max_disp = batch_max_disp(args.dataset, n_disp, args.max_disp)
-            left, right, disparity = left.to(device), right.to(device), disparity.to(device)
-            lms, rms = [m.to(device) for m in (lm1, lm2, lm3)], [m.to(device) for m in (rm1, rm2, rm3)]
-            torch.cuda.synchronize()
-            t0 = time.time()
-            pred = model(left, right, disparity, lms, rms, is_check=False, is_eval=bool(args.is_eval))[-1]
-            torch.cuda.synchronize()
-            dt = time.time() - t0
-            if args.is_eval:
-                epe, loss_3 = test_loss_func(pred, disparity, model.max_disp)
-                rec.append((bi, float(epe.mean().item()), float(loss_3.mean().item())))
-                print("[{}/{}]   evaluation cost time: {} - epe: {} - loss3: {}".format(bi, len(batches), dt, rec[-1][1],
-                                                                                      rec[-1][2]))
-            else:
-                for j, name in enumerate(names):
-                    write_png16(os.path.join(args.save2where, name + ".png"),
-                                disparity_to_uint16(pred[j:j + 1], int(ori_h[j]), int(ori_w[j])))
-                print("[{}/{}]   submission cost time: {}".format(bi, len(batches), dt))
+    run = run_pipelined if pipeline else run_default
+    rec = run(args, model, dataset, batches, lo, hi, device)            # (batch index, epe, loss_3)
     result = None
     if coll:
         # the per-batch metrics of every rank, once, as one all-gather of a fixed-size tensor over RCCL
@@ -200,6 +186,82 @@ def test(args, model=None):
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
     return result
+
+
+def run_default(args, model, dataset, batches, lo, hi, device):
+    """--pipeline 0: the batches lo .. hi-1 as the reference runs them -- host-preprocessed samples, the eager forward
+    between two synchronises, metrics or PNGs per batch.  Returns the (batch index, epe, loss_3) list."""
+    rec = []
+    for bi in range(lo, hi):
+        (left, right, disparity, _image, lm1, lm2, lm3, rm1, rm2, rm3, ori_h, ori_w, names, n_disp) = collate(
+            [dataset[i] for i in batches[bi]])
+        with torch.no_grad():
+            model.max_disp = batch_max_disp(args.dataset, n_disp, args.max_disp)
+            left, right, disparity = left.to(device), right.to(device), disparity.to(device)
+            lms, rms = [m.to(device) for m in (lm1, lm2, lm3)], [m.to(device) for m in (rm1, rm2, rm3)]
+            torch.cuda.synchronize()
+            t0 = time.time()
+            pred = model(left, right, disparity, lms, rms, is_check=False, is_eval=bool(args.is_eval))[-1]
+            torch.cuda.synchronize()
+            dt = time.time() - t0
+            if args.is_eval:
+                epe, loss_3 = test_loss_func(pred, disparity, model.max_disp)
+                rec.append((bi, float(epe.mean().item()), float(loss_3.mean().item())))
+                print("[{}/{}]   evaluation cost time: {} - epe: {} - loss3: {}".format(bi, len(batches), dt, rec[-1][1],
+                                                                                      rec[-1][2]))
+            else:
+                for j, name in enumerate(names):
+                    write_png16(os.path.join(args.save2where, name + ".png"),
+                                disparity_to_uint16(pred[j:j + 1], int(ori_h[j]), int(ori_w[j])))
+                print("[{}/{}]   submission cost time: {}".format(bi, len(batches), dt))
+    return rec
+
+
+def run_pipelined(args, model, dataset, batches, lo, hi, device):
+    """--pipeline 1: the batches lo .. hi-1 through decnet_amd.StereoEngine.  Samples come from the loaders' raw mode,
+    read by a pool of host threads (host work only: every HIP call is made by this thread).  With --is_eval the metric
+    sums of every batch stay on the device in one [n_batches, 3] float64 record (valid count, sum of errors, good count),
+    read once when everything has run; the per-batch lines are printed then.  Returns the (batch index, epe, loss_3) list."""
+    from concurrent.futures import ThreadPoolExecutor
+    from .engine import StereoEngine
+    from .imageio import metrics_from_sums
+    nb, is_eval = len(batches), bool(args.is_eval)
+    if hi <= lo:
+        return []
+    engine = StereoEngine(model, batch_size=max(len(b) for b in batches))
+    record = torch.zeros((nb, 3), dtype=torch.float64, device=device) if is_eval else None
+    t0 = time.time()
+    done = [0]
+
+    def write(results):
+        for (bi, names), disps, _ in results:
+            done[0] += 1
+            for name, img in zip(names, disps):
+                write_png16(os.path.join(args.save2where, name + ".png"), img)
+            print("[{}/{}]   submission cost time: {}".format(bi, nb, (time.time() - t0) / done[0]))
+
+    workers = min(16, max(1, args.workers))
+    with ThreadPoolExecutor(max_workers=workers) as pool:
+        order = [i for bi in range(lo, hi) for i in batches[bi]]
+        samples = prefetched(pool, dataset.__getitem__, order, 2 * engine.batch_size + workers)
+        for bi in range(lo, hi):
+            lefts, rights, disps, names, n_disp = zip(*[next(samples) for _ in batches[bi]])
+            engine.submit(lefts, rights, max_disp=batch_max_disp(args.dataset, n_disp, args.max_disp),
+                          gts=disps if is_eval else None, tag=(bi, names), sums_out=record[bi] if is_eval else None)
+            if not is_eval:
+                write(engine.results())
+        rest = engine.flush()
+        if not is_eval:
+            write(rest)
+    if not is_eval:
+        return []
+    dt = (time.time() - t0) / (hi - lo)
+    rec = []
+    for bi, sums in zip(range(lo, hi), record[lo:hi].cpu().numpy()):    # the one read-back
+        epe, loss_3 = metrics_from_sums(sums)
+        rec.append((bi, epe, loss_3))
+        print("[{}/{}]   evaluation cost time: {} - epe: {} - loss3: {}".format(bi, nb, dt, epe, loss_3))
+    return rec
 
 
 def batch_max_disp(dataset, n_disp, default):

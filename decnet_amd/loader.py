@@ -81,9 +81,28 @@ def _masks(img01_padded, stored, use_detail):
     return [torch.from_numpy(m.astype(np.float32)) for m in detail_detection(img01_padded)[::-1]]
 
 
+def exact_uint8(img, path):
+    """``img`` as uint8 if every value survives the round trip exactly, else ValueError naming ``path`` (the raw mode
+    hands the bytes to the device, which must see what the float path would have seen)."""
+    img = np.asarray(img)
+    if img.dtype == np.uint8:
+        return np.ascontiguousarray(img)
+    u8 = img.astype(np.uint8)
+    if not np.array_equal(u8.astype(img.dtype), img):
+        raise ValueError("%s: pixel values are not exact uint8 (raw mode needs integers in 0..255)" % path)
+    return np.ascontiguousarray(u8)
+
+
 class _Base(data.Dataset):
-    def __init__(self, use_detail=True, max_disp=192):
-        self.use_detail, self.n_disp = use_detail, max_disp
+    """raw=True (decnet_amd.engine's input): a sample is ``(left_u8, right_u8, disp, name, n_disp)`` -- the h x w x 3
+    uint8 views and the float32 disparity, unpadded, no float conversion, no masks."""
+
+    def __init__(self, use_detail=True, max_disp=192, raw=False):
+        self.use_detail, self.n_disp, self.raw = use_detail, max_disp, raw
+
+    def _raw_item(self, left, right, disp, name, n_disp, path):
+        return (exact_uint8(left, path), exact_uint8(right, path),
+                np.ascontiguousarray(disp, dtype=np.float32), name, n_disp)
 
     def _item(self, left_u8, right_u8, disp, name, n_disp, lmasks=None, rmasks=None):
         ori_h, ori_w = left_u8.shape[:2]
@@ -101,6 +120,8 @@ class NpyPairs(_Base):
     def __init__(self, root, split="test", is_training=False, img_size=(540, 960), policy="sceneflow", **kw):
         super().__init__(**kw)
         self.is_training, self.img_size, self.policy = is_training, tuple(img_size), policy
+        if self.raw and is_training:
+            raise ValueError("raw=True has no training branch (crop and augmentation work on float samples)")
         p = os.path.join(root, split)
         if os.path.isfile(p):
             self.paths = sorted(str(s) for s in np.load(p))
@@ -116,6 +137,8 @@ class NpyPairs(_Base):
         path = self.paths[i]
         arr = np.load(path)
         name = os.path.basename(path).split(".")[0]
+        if self.raw:
+            return self._raw_item(arr[..., 0:3], arr[..., 3:6], arr[..., 6], name, -1, path)
         d = os.path.dirname(path)
         mpath = os.path.join(d + "_mask", name)
         lm = rm = None
@@ -180,6 +203,9 @@ class MiddleburyPickles(_Base):
         disp = np.zeros(left.shape[:2], np.float32) if disp is None else np.array(disp, dtype=np.float32)
         disp[~np.isfinite(disp)] = 0                                       # MiddleburyMask.py:128
         name = self.files[i].split(".pkl")[0]
+        if self.raw:
+            return self._raw_item(left, right, disp, self.files[i].split(".")[0], int(raw["ndisp"]),
+                                  os.path.join(self.datapath, self.split, self.files[i]))
         lm = rm = None
         mpath = os.path.join(self.datapath, self.split + "_mask", name)
         if os.path.exists(mpath):
@@ -213,6 +239,8 @@ class PairDirectory(_Base):
         else:
             disp = np.zeros(left.shape[:2], np.float32)
         n = read_ndisp(os.path.join(d, "calib.txt"))
+        if self.raw:
+            return self._raw_item(left, right, disp, self.names[i], n, d)
         return self._item(left, right, disp, self.names[i], n)            # n <= 0: no calib.txt, eval keeps --max_disp
 
 

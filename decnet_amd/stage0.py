@@ -53,6 +53,25 @@ class CachesWeights:
         for a in self._CACHE_ATTRS:
             self.__dict__.pop(a, None)
 
+    def cache_tensors(self):
+        """Every tensor the caches of this module hold now (packed weights, folded scales, workspaces), nested in dicts,
+        lists and tuples to any depth.  Who captures a HIP graph keeps them: the module replaces a cache when another
+        shape, range or weight arrives, and the graph goes on reading the old addresses (decnet_amd.engine).  A cache
+        that keeps tensors in another kind of container has to override this."""
+        found, seen, todo = [], set(), [self.__dict__.get(a) for a in self._CACHE_ATTRS]
+        while todo:
+            v = todo.pop()
+            if id(v) in seen:
+                continue
+            seen.add(id(v))
+            if isinstance(v, torch.Tensor):
+                found.append(v)
+            elif isinstance(v, dict):
+                todo.extend(v.values())
+            elif isinstance(v, (list, tuple)):
+                todo.extend(v)
+        return found
+
     def __getstate__(self):
         state = super().__getstate__()
         for a in self._CACHE_ATTRS:

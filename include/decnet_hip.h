@@ -455,6 +455,35 @@ int decnet_ncdhw_to_ndhwc(const float *src, float *dst, int B, int C, int D, int
 int decnet_ndhwc_to_ncdhw(const float *src, float *dst, int B, int C, int D, int H, int W,
                           void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * The image boundary: uint8 views in, uint16 disparity and evaluation sums out.  None of the three allocates,
+ * synchronises or asks about the stream (all run under stream capture); no pointer needs more than the alignment of
+ * its element type, and the uint8 / uint16 buffers none at all.  DECNET_ERR_BAD_SHAPE: a non-positive size, H < h,
+ * W < w, or B * H * W (times 3 for the image) >= 2^31.  The h x w image sits at the BOTTOM RIGHT of the H x W plane
+ * (the reference pads on the top and left, demo.py:75-81).
+ *
+ * decnet_preprocess_u8 -- demo.py:75-89 (padding + transform), loader/SceneflowMask.py:118-130,152-153,206-210.
+ *   img    [B,h,w,3] uint8, interleaved RGB
+ *   table  [256][3]  fp32, device: table[v][c] = what the host path makes of pixel value v in channel c.  The caller
+ *                    builds it (decnet_amd.imageio.normalise_table: the loader's own numpy expressions), so the output
+ *                    is bit-equal to the host path.
+ *   out    [B,3,H,W] fp32: out[b,c,y,x] = table[img[b, y-(H-h), x-(W-w), c]][c] inside the image, table[0][c] in the
+ *                    padding (the reference pads with zeros BEFORE it normalises).                                  */
+int decnet_preprocess_u8(const unsigned char *img, const float *table, float *out, int B, int h, int w, int H, int W,
+                         void *stream);
+/* demo.py:191-197.  pred [B,H,W] fp32 -> out [B,h,w] uint16 = (uint16) min(max(pred * 256, 0), 65535), truncated toward
+ * zero, of the bottom-right window (a NaN gives 0). */
+int decnet_disparity_to_u16(const float *pred, unsigned short *out, int B, int H, int W, int h, int w, void *stream);
+/* test_loss_func (modules/loss.py:427-437), as sums.  pred [B,H,W]; gt [B,h,w] UNPADDED, compared with the bottom-right
+ * window of pred (the loader's padded ground truth is 0 in the padding, hence invalid: the same pixels take part).
+ *   partials [B,h,3] fp32, per row, over the pixels with 0 < gt < max_disp:  the count of those pixels,
+ *            sum |pred - gt|, the count with |pred - gt| < 3 || |pred - gt| < 0.05f * gt.
+ * Fixed summation order, no atomics: the same bits on every call.  A NaN prediction gives a NaN sum and is not counted
+ * as good.  EPE = sum of [1] / sum of [0], loss_3 = 100 - 100 * sum of [2] / sum of [0] (reduce in float64; the counts
+ * are exact for w < 2^24). */
+int decnet_disparity_metrics(const float *pred, const float *gt, float max_disp, float *partials, int B, int H, int W,
+                             int h, int w, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
