@@ -4,6 +4,7 @@
 * stage-0 dense cost volume -> Conv3d aggregation -> soft-argmax
   (reference modules/submodule.py GetCostVolume / CostRegNetNoDown / disparity_regression)
 * StereoEngine: uint8 pairs in, uint16 disparity out -- the whole network as one HIP graph per shape, copies pipelined
+* Loss: the multi-stage training loss (reference modules/loss.py), one fused kernel pair per pyramid level
 
 Host side is Python on PyTorch-ROCm (device memory + streams only); all arithmetic runs in
 hand-written HIP kernels behind the C ABI of include/decnet_hip.h.  No CPU fallback.
@@ -15,9 +16,11 @@ from .modules.SparseVar.modules.SpaVar import SpaVar  # noqa: F401
 from .modules.SparseVar.functions.SpaVar import SpaVarFunction  # noqa: F401
 from .ops import spamatvar_forward, spamatvar_forward_bits  # noqa: F401
 from .engine import StereoEngine  # noqa: F401
+from .loss import Loss, StageLossFunction  # noqa: F401
 from .stage0 import (CostRegNetNoDown, GetCostVolume, Stage0, disparity_regression,  # noqa: F401
                      drop_weight_caches, get_disp_samples)
 
 __all__ = ["SpaMat", "SpaVar", "SpaMatFunction", "SpaVarFunction", "spamatvar_forward", "spamatvar_forward_bits",
            "GetCostVolume", "CostRegNetNoDown", "disparity_regression", "get_disp_samples",
-           "Stage0", "DecnetHipError", "version", "drop_weight_caches", "StereoEngine"]
+           "Stage0", "DecnetHipError", "version", "drop_weight_caches", "StereoEngine", "Loss",
+           "StageLossFunction"]

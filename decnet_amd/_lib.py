@@ -84,6 +84,8 @@ SIGNATURES = {
     "decnet_preprocess_u8": [_P] * 3 + [_I] * 5 + [_P],
     "decnet_disparity_to_u16": [_P] * 2 + [_I] * 5 + [_P],
     "decnet_disparity_metrics": [_P, _P, _F, _P] + [_I] * 5 + [_P],
+    "decnet_stage_loss_forward": [_P] * 7 + [_F, _F, _I] + [_P] * 3 + [_I] * 3 + [_P],
+    "decnet_stage_loss_backward": [_P] * 7 + [_F, _F, _I] + [_P] * 7 + [_I] * 3 + [_P],
 }
 
 

@@ -214,3 +214,72 @@ def spamatvar_forward(ref, tar, rmask, tmask, max_disp, out=None):
           ref.data_ptr(), tar.data_ptr(), rmask.data_ptr(), tmask.data_ptr(), o.data_ptr(),
           v.data_ptr(), s.data_ptr(), m.data_ptr())
     return o, v, s, m
+
+
+# ---- one level of the multi-stage training loss (csrc/loss.hip) ------------------------------------------------------
+_F64 = torch.float64
+
+
+def _chk64(name, t, shape):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor" % name)
+    if not t.is_cuda:
+        raise _lib.DecnetHipError("%s is on %s: decnet_amd runs on the MI355X HIP path only (no CPU fallback)"
+                                  % (name, t.device))
+    if t.dtype != _F64:
+        raise TypeError("%s must be float64, got %s" % (name, t.dtype))
+    if not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise ValueError("%s must be a contiguous float64 tensor of shape %s" % (name, tuple(shape)))
+    return t
+
+
+def _loss_planes(pred, dense, sparse, fusion, soft_mask, left_mask, gt):
+    _chk("pred", pred)
+    if pred.dim() != 3:
+        raise ValueError("pred must be [B,H,W]")
+    shape = pred.shape
+    _chk("gt", gt, shape)
+    opt = (("dense", dense), ("sparse", sparse), ("fusion", fusion), ("soft_mask", soft_mask), ("left_mask", left_mask))
+    given = [t is not None for _, t in opt]
+    if any(given) and not all(given):
+        raise ValueError("dense, sparse, fusion, soft_mask and left_mask are given together (the composite form) or not "
+                         "at all (the simple form)")
+    for n, t in opt:
+        if t is not None:
+            _chk(n, t, shape)
+    _same_device(pred, gt, *(t for _, t in opt))
+    return tuple(shape), [0 if t is None else t.data_ptr() for _, t in opt]
+
+
+def stage_loss_forward(pred, dense, sparse, fusion, soft_mask, left_mask, gt, gt_max, down_size, skip_rows, row_sums,
+                       sums, terms):
+    """decnet_stage_loss_forward: planes [B,H,W] float32 (dense ... left_mask all None: the simple form) ->
+    row_sums [B*H,8] float64 (scratch), sums [8] float64, terms [5] float32 (dense, sparse, soft-mask mean, fusion,
+    pred)."""
+    (B, H, W), opt = _loss_planes(pred, dense, sparse, fusion, soft_mask, left_mask, gt)
+    _chk64("row_sums", row_sums, (B * H, 8))
+    _chk64("sums", sums, (8,))
+    _chk("terms", terms, (5,))
+    with _on_device(pred):
+        rc = _fn("decnet_stage_loss_forward")(pred.data_ptr(), *opt, gt.data_ptr(), float(gt_max), float(down_size),
+                                              int(skip_rows), row_sums.data_ptr(), sums.data_ptr(), terms.data_ptr(),
+                                              B, H, W, _stream(pred))
+    _lib.check(rc, "decnet_stage_loss_forward")
+    return terms
+
+
+def stage_loss_backward(pred, dense, sparse, fusion, soft_mask, left_mask, gt, gt_max, down_size, skip_rows, sums,
+                        grad_terms, g_pred=None, g_dense=None, g_sparse=None, g_fusion=None, g_soft=None):
+    """decnet_stage_loss_backward: every gradient plane that is not None is written in full."""
+    (B, H, W), opt = _loss_planes(pred, dense, sparse, fusion, soft_mask, left_mask, gt)
+    _chk64("sums", sums, (8,))
+    _chk("grad_terms", grad_terms, (5,))
+    outs = []
+    for n, t in (("g_pred", g_pred), ("g_dense", g_dense), ("g_sparse", g_sparse), ("g_fusion", g_fusion),
+                 ("g_soft", g_soft)):
+        outs.append(0 if t is None else _chk(n, t, (B, H, W)).data_ptr())
+    with _on_device(pred):
+        rc = _fn("decnet_stage_loss_backward")(pred.data_ptr(), *opt, gt.data_ptr(), float(gt_max), float(down_size),
+                                               int(skip_rows), sums.data_ptr(), grad_terms.data_ptr(), *outs,
+                                               B, H, W, _stream(pred))
+    _lib.check(rc, "decnet_stage_loss_backward")

@@ -484,6 +484,45 @@ int decnet_disparity_to_u16(const float *pred, unsigned short *out, int B, int H
 int decnet_disparity_metrics(const float *pred, const float *gt, float max_disp, float *partials, int B, int H, int W,
                              int h, int w, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * One pyramid level of the multi-stage training loss (Loss.multi_stage_regression_Uploss, modules/loss.py:168-242) and
+ * its gradient.  Neither entry allocates, synchronises or asks about the stream (both run under stream capture); every
+ * plane is [B,H,W] fp32 at any float alignment, inputs are never modified, and the results depend neither on the
+ * alignment of a plane nor on the launch shape.  DECNET_ERR_BAD_SHAPE: a non-positive size, B * H * W >= 2^31 or
+ * skip_rows < 0; nothing is launched then.
+ *   gt         the ground truth ALREADY at this level's resolution (the caller downsamples it)
+ *   valid    = gt > 0 && gt < gt_max && y >= skip_rows          (skip_rows: the if_overmask rows, loss.py:204-205)
+ *   whole    = valid && left_mask == 1
+ *   term(a)  = smooth-L1 (beta 1) of d = a * down_size - gt * down_size, the products and d rounded to fp32
+ *   means:     pred, dense, fusion over valid; sparse over whole; soft_mask over left_mask == 1 (it ignores valid,
+ *              loss.py:235).  A mean over no pixels is NaN.  A pixel outside a mask is selected out: a NaN there reaches
+ *              no sum; a NaN inside a mask makes its term NaN.
+ * dense, sparse, fusion, soft_mask, left_mask all NULL: the simple form of stage 0 and of the stages >= stop_stage_id
+ * (loss.py:207-211): only the pred term, the other four written as 0.  Some but not all of them NULL:
+ * DECNET_ERR_NULL_POINTER.
+ *
+ * decnet_stage_loss_forward: two launches.  Per row (a wave each; every lane accumulates in float64 from its first
+ * element on, the lanes are added in a fixed butterfly), then one workgroup that adds the rows in a fixed order.
+ *   row_sums [B*H][8] float64 scratch; per row: n_valid, n_whole, n_left, S_pred, S_dense, S_sparse, S_fusion, S_soft
+ *   sums     [8]      float64: their totals (what the backward entry reads)
+ *   terms    [5]      fp32: dense, sparse, soft-mask mean, fusion, pred -- the order the reference appends them to
+ *                     loss_list (loss.py:233-237) -- each the fp32 of the float64 quotient.
+ * decnet_stage_loss_backward: one launch; counts and upstream gradients are read from device memory.
+ *   sums       [8] as the forward entry left them;  grad_terms [5] fp32, device: d(loss) / d(terms[k])
+ *   g_*        NULL (skipped) or [B,H,W], written in full: grad_terms[k] * down_size * clamp(d, -1, 1) / n inside the
+ *              term's mask, grad_terms[2] / n_left for the soft mask, 0 elsewhere -- and 0 everywhere where the term's
+ *              count is 0 (the gradient of an empty gather), and for the four absent terms of the simple form.
+ * ------------------------------------------------------------------------------------- */
+int decnet_stage_loss_forward(const float *pred, const float *dense, const float *sparse, const float *fusion,
+                              const float *soft_mask, const float *left_mask, const float *gt, float gt_max,
+                              float down_size, int skip_rows, double *row_sums, double *sums, float *terms, int B, int H,
+                              int W, void *stream);
+int decnet_stage_loss_backward(const float *pred, const float *dense, const float *sparse, const float *fusion,
+                               const float *soft_mask, const float *left_mask, const float *gt, float gt_max,
+                               float down_size, int skip_rows, const double *sums, const float *grad_terms, float *g_pred,
+                               float *g_dense, float *g_sparse, float *g_fusion, float *g_soft, int B, int H, int W,
+                               void *stream);
+
 #ifdef __cplusplus
 }
 #endif
