@@ -456,6 +456,8 @@ __global__ __launch_bounds__(256) void wino_output_transform(
 // later) travels in a private planar layout R [sample][quad][D][H][4][W | 1] = a dump of the workgroup's LDS.
 // Phase 1 is wino_output_stream6 per (tile, channel); phase 2 is wino_input_body with two threads per
 // (tile, channel), LDS instead of x.
+// V may BE M (in place, not __restrict__): workgroup (b, cq) reads M and writes V at the same offsets (moff == voff, the
+// same point stride), no other workgroup touches them, and the barrier between the phases has every M value in LDS first.
 constexpr int MID_THREADS = 512;
 
 template <int HALF, int NCH = 4>
@@ -607,7 +609,7 @@ __device__ __forceinline__ void wino_output_phase(__amdgpu_buffer_rsrc_t mr, flo
 }
 
 __global__ __launch_bounds__(MID_THREADS) void wino_mid_transform(
-    const float *__restrict__ M, float *__restrict__ V, const float *__restrict__ scale,
+    const float *M, float *V, const float *__restrict__ scale,
     const float *__restrict__ shift, const float *__restrict__ res_in, float *__restrict__ res_out, Tiling g,
     int C, int nt, int relu) {
     extern __shared__ float ys[];                       // [D][H][4][Wp]
@@ -1028,9 +1030,15 @@ __global__ void wino_split_weights(const float *__restrict__ U, int *__restrict_
         *reinterpret_cast<i32x4 *>(Ub + ((((size_t)pt * NP2 + pair) * 3 + term) * W_BN + co) * 16 + 4 * kq) = t[term];
 }
 
-template <int WM, int NPAIR, int TM = 3>
+// INPLACE: Mb == Vb (Ci == Co, the same layout on both sides: gemm_dispatch checks it).  Workgroup (pt, mb) reads
+// V[pt][every chunk][its WM * 48 tiles] and writes M[pt][every group][the same tiles]: with Ci == Co and equal strides
+// that is one address set, disjoint from every other workgroup's, so the only hazard is inside the workgroup -- the two
+// waves of a row block (same wm) read the same V rows and each stores half of the channel groups over them.  One
+// workgroup barrier between the last V load and the first M store orders that.  Vb and Mb are not __restrict__ for that
+// reason; the two-buffer and v_shared instantiations (INPLACE = 0) have no barrier.
+template <int WM, int NPAIR, int TM = 3, int INPLACE = 0>
 __global__ __launch_bounds__(WM * 128) __attribute__((amdgpu_waves_per_eu(TM > 3 ? 1 : TM == 2 ? 3 : 2, TM > 3 ? 1 : TM == 2 ? 3 : 2))) void wino_gemm_bf16x3(
-    const float *__restrict__ Vb, const int *__restrict__ Ubb, float *__restrict__ Mb, int nt, int Ci,
+    const float *Vb, const int *__restrict__ Ubb, float *Mb, int nt, int Ci,
     int Co, int np, int swz, int v_ms, int v_kqs, int m_ms, int m_kqs, int v_shared) {
     // v_shared: every point multiplies the SAME V (decnet_tap_gemm).  v_ms / v_kqs, m_ms / m_kqs: bytes between consecutive tiles and between the four 4-channel groups of a
     // 16-channel chunk in V and in M: (64, 16) = the chunk-major layout [chunk][tile][16] of the head of this
@@ -1046,6 +1054,8 @@ __global__ __launch_bounds__(WM * 128) __attribute__((amdgpu_waves_per_eu(TM > 3
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wm = wave >> 1, wn = wave & 1, i16 = lane & 15, kq = lane >> 4;
     const int m0 = (mb * WM + wm) * (TM * 16);
+    // a whole wave pair of the half-empty last row block ends here, before the INPLACE barrier: a wave that has ended
+    // is not waited for at a barrier, and both waves of a pair (the only ones that share rows) take the same branch
     if (m0 >= nt) return;
     const int KC = (Ci + 15) >> 4, CG = (Co + 15) >> 4;
     const int v_chunk = nt * 64, v_point = v_shared ? 0 : KC * v_chunk, m_point = CG * v_chunk;
@@ -1128,6 +1138,10 @@ __global__ __launch_bounds__(WM * 128) __attribute__((amdgpu_waves_per_eu(TM > 3
             __builtin_amdgcn_sched_barrier(0);
         }
     }
+    // Sufficient because every real V load of this wave has been CONSUMED by a split3 above, so its data has returned
+    // before the wave can arrive here; the only load still outstanding, load_v(NPAIR), is all out of bounds and touches
+    // no memory.  Past the barrier that holds for every wave, and the other wave of the pair may overwrite the rows
+    if (INPLACE) __syncthreads();
     const int pb = pt * m_point + kq * m_kqs;
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
@@ -1163,13 +1177,22 @@ int launch_gemm(const float *V, const float *U, float *M, int nt, int Ci, int Co
     return decnet_launch_status();
 }
 
-// v_quad / m_quad: V / M in the quad-major layout (wino_gemm_bf16x3 only)
+// v_quad / m_quad: V / M in the quad-major layout (wino_gemm_bf16x3 only).
+// M may BE V (in place) exactly when wino_gemm_bf16x3 runs, Ci == Co and both sides have the same layout; any other
+// overlap of the two ranges is DECNET_ERR_UNSUPPORTED with nothing launched.
 int gemm_dispatch(const float *V, const float *U, float *M, int nt, int Ci, int Co, int np,
                   hipStream_t s, int v_quad = 0, int m_quad = 0) {
-    if (gemm_bf16x3() && Ci == 216) {
+    const bool bf16 = gemm_bf16x3() && Ci == 216;
+    const uintptr_t v0 = (uintptr_t)V, v1 = v0 + (size_t)np * nt * pad16(Ci) * 4;
+    const uintptr_t m0 = (uintptr_t)M, m1 = m0 + (size_t)np * nt * pad16(Co) * 4;
+    const bool inplace = v0 == m0;
+    if (v0 < m1 && m0 < v1 && !(inplace && bf16 && Ci == Co && !v_quad == !m_quad)) return DECNET_ERR_UNSUPPORTED;
+    if (bf16) {
         constexpr int swz = 1;                          // XCD-aware block order
         const int *Ub = reinterpret_cast<const int *>(U + (size_t)np * pad16(Ci) * W_BN);   // split copy behind U^T
-        hipLaunchKernelGGL((wino_gemm_bf16x3<2, 7>), dim3(ceil_div(nt, 96), np), dim3(256), 0, s, V, Ub, M, nt, Ci,
+        // (the barrier-less kernel must never run in place: the check above has refused every overlap except v0 == m0)
+        const auto fn = inplace ? wino_gemm_bf16x3<2, 7, 3, 1> : wino_gemm_bf16x3<2, 7, 3, 0>;
+        hipLaunchKernelGGL(fn, dim3(ceil_div(nt, 96), np), dim3(256), 0, s, V, Ub, M, nt, Ci,
                            Co, np, swz, v_quad ? 16 : 64, v_quad ? 16 * nt : 16, m_quad ? 16 : 64, m_quad ? 16 * nt : 16, 0);
         return decnet_launch_status();
     }
@@ -1240,6 +1263,14 @@ bool stack_ok(int B, int D, int H, int W, int C, int variant) {
     return (double)T * pad16(C) * 4 * 216 < 2147483647.0 && (double)B * D * H * W * C * 4 < 2147483647.0;
 }
 
+// 1 (the default): the quad-major layers of the fused stack keep V and M in ONE buffer (wino_gemm_bf16x3<.., 1> and
+// wino_mid_transform in place), so that the distinct bytes between two uses of a V / M line stay under the last-level
+// cache's size; DECNET_WINO_INPLACE=0: two buffers.  The same values either way.  Read once per process.
+static int stack_inplace() {
+    static const int k = [] { const char *e = getenv("DECNET_WINO_INPLACE"); return e && !strcmp(e, "0") ? 0 : 1; }();
+    return k;
+}
+
 size_t head_lds_bytes(int D, int H, int W) {
     return stack_lds_bytes(D, H, W) + ((size_t)8 * H * W + 3 * (W + D) + 3 * H + 4 * H * head_rw_pitch(W, D)) * 4;
 }
@@ -1292,14 +1323,17 @@ int conv_stack(const float *x, const float *left, const float *right, const floa
     for (int i = 0; i < n_layers; ++i) {
         const bool last = i == n_layers - 1;
         // V of layer 0 comes from wino_input_transform (chunk major) unless the head kernel forms it, M of the last layer
-        // goes to wino_output_transform (chunk major); everything between is quad major
-        if ((rc = gemm_dispatch(V, u[i], M, nt, C, C, NP, s, i > 0 || !x, !last))) return rc;
+        // goes to wino_output_transform (chunk major); everything between is quad major.  A layer that is quad major on
+        // both sides multiplies in place (Mi == V); the chunk-major ends go through the second region
+        const int v_quad = i > 0 || !x, m_quad = !last;
+        float *Mi = stack_inplace() && v_quad && m_quad ? V : M;
+        if ((rc = gemm_dispatch(V, u[i], Mi, nt, C, C, NP, s, v_quad, m_quad))) return rc;
         if (last) {
             const size_t n = (size_t)nt * pad16(C);
             hipLaunchKernelGGL((wino_output_transform<6, 6, 6, 1>), dim3((unsigned)((n + 255) / 256), 1), dim3(256), 0, s,
                                M, scale[i], shift[i], (const float *)nullptr, y, g, C, 1, 0, nt, bytes);
         } else {
-            hipLaunchKernelGGL(wino_mid_transform, dim3((unsigned)(B * ((C + 3) / 4))), dim3(MID_THREADS), lds, s, M, V,
+            hipLaunchKernelGGL(wino_mid_transform, dim3((unsigned)(B * ((C + 3) / 4))), dim3(MID_THREADS), lds, s, Mi, V,
                                scale[i], shift[i], i == res_dst ? R : (const float *)nullptr,
                                i == res_src ? R : (float *)nullptr, g, C, nt, 1);
         }

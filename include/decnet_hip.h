@@ -228,7 +228,11 @@ int decnet_conv3d_wino_pack_weight(const float *w_oidhw, float *u, int Co, int C
 size_t decnet_conv3d_wino_workspace_floats(int B, int D, int H, int W, int Ci, int Co, int variant);
 /* its GEMM stage alone: M[xi] = V[xi] * U[xi] for every transform point xi, 16 channels (64 bytes)
  * being the unit of all three layouts:
- *   V [points][ceil(Ci/16)][nt][16] (transformed input tiles), M [points][ceil(Co/16)][nt][16]. */
+ *   V [points][ceil(Ci/16)][nt][16] (transformed input tiles), M [points][ceil(Co/16)][nt][16].
+ * In place: M == V is accepted exactly when the bf16x3 kernel runs (Ci = 216, DECNET_WINO_GEMM unset or bf16x3) and
+ * Ci == Co, so that V and M are one layout; the result is bit for bit that of the two-buffer call.  Every other overlap
+ * of the two ranges (M inside V's range but not equal to it, Ci != Co, the fp32 kernels) returns
+ * DECNET_ERR_UNSUPPORTED with nothing launched. */
 int decnet_conv3d_wino_gemm(const float *V, const float *u, float *M, int nt, int Ci, int Co,
                             int variant, void *stream);
 int decnet_conv3d_wino_bn_act(const float *x, const float *u, const float *scale,
