@@ -92,6 +92,23 @@ def build_ubench(force=False):
     return outs[0]
 
 
+TESTHOOKS_SRC = os.path.join(os.path.dirname(HERE), "tests", "support", "lds_poison.hip")
+TESTHOOKS_PATH = os.path.join(LIB_DIR, "libdecnet_testhooks.so")
+
+
+def build_testhooks(force=False):
+    """decnet_amd/lib/libdecnet_testhooks.so from tests/support/lds_poison.hip: the LDS poison, its probe and the planted
+    bug of tests/_lds_poison.py.  Test support only: a library of its own, no part of libdecnet_hip.so or its header."""
+    out = TESTHOOKS_PATH
+    if force or not os.path.exists(out) or os.path.getmtime(out) < os.path.getmtime(TESTHOOKS_SRC):
+        hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+        os.makedirs(LIB_DIR, exist_ok=True)
+        subprocess.check_call([hipcc, "--offload-arch=" + ARCH, "-O3", "-w", "-shared", "-fPIC", TESTHOOKS_SRC,
+                               "-o", out + ".tmp"])
+        os.replace(out + ".tmp", out)
+    return out
+
+
 # ---- the compiled drop-in modules (SURVEY.md 8b "Build boundary") --------------------------------------------
 PYBIND_SRC = os.path.join(CSRC, "pybind")
 PYBIND_MODULES = {          # module name -> (source, directory of the reference layout it lands in)

@@ -1,7 +1,8 @@
 """Guarded placement of device buffers for the edge tests through the C ABI (tests/test_trunk_edges_gpu.py,
 tests/test_stage0_edges_gpu.py): every buffer is a window of a larger one, filled with a sentinel outside the window,
 16-byte aligned or at an odd float offset; `Place.check` verifies margins, unmodified inputs and fully written outputs
-(`Place.check_untouched`: outputs left alone by a rejected call), `_both` runs a case at both placements and requires bit-identical results."""
+(`Place.check_untouched`: outputs left alone by a rejected call), `_both` runs a case at both placements and requires bit-identical results,
+then repeats both with LDS poisoned before every entry (tests/_lds_poison.py)."""
 import ctypes
 import math
 
@@ -14,8 +15,10 @@ ERR_UNSUPPORTED, ERR_MISALIGNED = -3, -5
 
 
 def _L():
+    """The library handle; while tests/_lds_poison.py has a pattern set, a proxy that poisons LDS before every entry."""
+    import _lds_poison
     from decnet_amd import _lib
-    return _lib.lib()
+    return _lds_poison.wrap(_lib.lib())
 
 
 def _st():
@@ -109,9 +112,13 @@ def _bn(cout, g, big=1.0):
 
 
 def _both(run, *args):
-    """run(*args, aligned) at both placements; the results must be bit-identical.  Returns the aligned results."""
+    """run(*args, aligned) at both placements; the results must be bit-identical.  Then both placements again under each
+    LDS poison pattern (tests/_lds_poison.py): bit-identical to the unpoisoned aligned results, which are returned."""
+    import _lds_poison
     a = run(*args, aligned=True)
     u = run(*args, aligned=False)
     for k in a:
         assert _bits_equal(a[k], u[k]), "%s differs between aligned and unaligned placement" % k
+    _lds_poison.hooks()
+    _lds_poison.sweep(lambda aligned: run(*args, aligned=aligned), a)
     return a

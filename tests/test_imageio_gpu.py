@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import _lds_poison
 from test_imageio_cpu import metrics_formula, u16_formula
 
 pytestmark = pytest.mark.gpu
@@ -56,6 +57,17 @@ class Guarded:
                 assert torch.equal(_bits(buf[off:off + n].cpu()), host), "an input was modified"
 
 
+def _poisoned(run, base):
+    """run(aligned) -> host array, at both placements with LDS poisoned before the entry (tests/_lds_poison.py: the package's
+    handle replaced by the poisoning proxy), under each pattern: the same bytes as `base`, the unpoisoned aligned result."""
+    for aligned in (True, False):
+        for pat in _lds_poison.PATTERNS:
+            with _lds_poison.package(pat):
+                got = run(aligned)
+            assert np.array_equal(np.asarray(got).view(np.uint8), np.asarray(base).view(np.uint8)), \
+                "result differs under %s, aligned=%s" % (_lds_poison.name(pat), aligned)
+
+
 def _images(B, h, w, seed):
     rng = np.random.RandomState(seed)
     img = rng.randint(0, 256, (B, h, w, 3)).astype(np.uint8)
@@ -94,6 +106,15 @@ def test_preprocess_is_the_host_path_bit_for_bit(hw, HW, B, table):
         assert torch.equal(got[aligned].view(torch.int32), want.view(torch.int32)), "aligned=%s" % aligned
     assert torch.equal(got[True].view(torch.int32), got[False].view(torch.int32))
 
+    def again(aligned):
+        g = Guarded(dev, aligned)
+        out = g.out((B, 3, H, W), torch.float32)
+        out.fill_(float("nan"))
+        imageio.preprocess_u8(g.inp(torch.from_numpy(img).to(dev)), g.inp(table.to(dev)), out)
+        g.check()
+        return out.cpu().numpy()
+    _poisoned(again, got[True].numpy())
+
 
 def _pred(B, H, W, seed):
     rng = np.random.RandomState(seed)
@@ -122,6 +143,14 @@ def test_u16_is_disparity_to_uint16(hw, HW, B):
         got[aligned] = out.cpu().numpy().view(np.uint16)
         assert np.array_equal(got[aligned], want), "aligned=%s" % aligned
     assert np.array_equal(got[True], got[False])
+
+    def again(aligned):
+        g = Guarded(dev, aligned)
+        out = g.out((B, h, w), torch.int16)
+        imageio.disparity_to_u16(g.inp(torch.from_numpy(pred).to(dev)), out)
+        g.check()
+        return out.cpu().numpy()
+    _poisoned(again, got[True])
 
 
 @pytest.mark.parametrize("hw,HW", [((26, 28), (27, 54)), ((40, 101), (54, 108))])
@@ -182,6 +211,15 @@ def test_metrics_counts_exact_and_sums_within_fp32_summation(hw, HW, B):
         if h > 3:
             assert not p[0, 3].any()
     assert np.array_equal(got[True].view(np.int32), got[False].view(np.int32))
+
+    def again(aligned):
+        g = Guarded(dev, aligned)
+        part = g.out((B, h, 3), torch.float32)
+        part.fill_(float("nan"))
+        imageio.disparity_metrics(g.inp(torch.from_numpy(pred).to(dev)), g.inp(torch.from_numpy(gt).to(dev)), D, part)
+        g.check()
+        return part.cpu().numpy()
+    _poisoned(again, got[True])
     epe, l3 = imageio.metrics_from_partials(torch.from_numpy(got[True]))
     n = want[..., 0].sum()
     assert abs(epe - want[..., 1].sum() / n) <= (w - 1) * 2.0 ** -24 * epe

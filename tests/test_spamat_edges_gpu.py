@@ -35,6 +35,7 @@ import zlib
 import pytest
 import torch
 
+import _lds_poison
 import _spamat_ref as R
 from _placement import ERR_UNSUPPORTED, Place, _bits_equal, _L, _st
 
@@ -430,6 +431,8 @@ def test_spamat_edges(dev, case):
     u = run(case, "all")
     for k in a:
         assert _bits_equal(a[k], u[k]), "%s: %s differs between aligned and unaligned placement" % (case[:5], k)
+    # both placements again with LDS poisoned before each of the six entries, under each pattern: bit-identical to `a`
+    _lds_poison.sweep(lambda mis: run(case, mis), a, placements=((None, "aligned"), ("all", "unaligned")))
     if case[8]:
         assert case[3] % 4 == 0
         for grp in GROUPS:

@@ -23,6 +23,7 @@ for _p in (os.path.join(HERE, "golden"), HERE, os.path.dirname(HERE)):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
+import _lds_poison                                                      # noqa: E402
 import test_spamat_edges_gpu as E                                        # noqa: E402
 from _placement import ERR_MISALIGNED, ERR_UNSUPPORTED, SENT, Place, _bits_equal, _L, _st   # noqa: E402
 
@@ -143,6 +144,16 @@ def test_ws_entries_equal_the_legacy_entries_bit_for_bit(dev, case):
     for k in legacy:
         assert _bits_equal(un[k], legacy[k]), "%s: %s differs with the tensors at an odd float offset" % (case[:5], k)
     E.check_values(case, got)
+
+
+# one wide case per route: dense rows in 2 bands; half-dense rows (the compacted kernels) in 3 bands, B = 2; sparse rows
+# with C = 24 and W < D (bands of empty candidates)
+@pytest.mark.parametrize("i", [0, 2, 3], ids=[IDS[0], IDS[2], IDS[3]])
+def test_ws_entries_do_not_depend_on_what_lds_held(dev, i):
+    """The forward and backward `_ws` entries with LDS poisoned before each (tests/_lds_poison.py), at both placements and
+    under each pattern: bit-identical to the unpoisoned aligned run."""
+    base, _ = run_ws(CASES[i], True)
+    _lds_poison.sweep(lambda aligned: run_ws(CASES[i], aligned)[0], base)
 
 
 def test_query_zero_means_the_existing_entry(dev):

@@ -135,6 +135,16 @@ def test_gemm_in_place_is_the_two_buffer_gemm(dev, u216, nt):
     for i, X in enumerate(runs):
         assert torch.equal(_bits(X), _bits(M)), "in-place run %d differs from the two-buffer result" % i
     assert torch.equal(_bits(runs[0]), _bits(runs[1])) and torch.equal(_bits(runs[1]), _bits(runs[2]))
+    # both forms again with LDS poisoned immediately before the GEMM: the result does not depend on what LDS held
+    import _lds_poison
+    for pat in _lds_poison.PATTERNS:
+        P = _lds_poison.PoisonedLib(L, pat)
+        X, M2 = V.clone(), torch.full_like(V, float("nan"))
+        assert P.decnet_conv3d_wino_gemm(V.data_ptr(), u216.data_ptr(), M2.data_ptr(), nt, C, C, 2, None) == 0
+        assert P.decnet_conv3d_wino_gemm(X.data_ptr(), u216.data_ptr(), X.data_ptr(), nt, C, C, 2, None) == 0
+        torch.cuda.synchronize()
+        assert torch.equal(_bits(M2), _bits(M)), "two-buffer GEMM differs under %s" % _lds_poison.name(pat)
+        assert torch.equal(_bits(X), _bits(M)), "in-place GEMM differs under %s" % _lds_poison.name(pat)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
