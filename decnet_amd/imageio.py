@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .ops import _fn, _on_device, _stream
+from .ops import _call  # noqa: F401  (tests/test_imageio_gpu.py calls imageio._call)
 
 _U16 = (torch.int16,) + ((torch.uint16,) if hasattr(torch, "uint16") else ())     # two-byte integers: the bits are uint16
 
@@ -42,12 +42,6 @@ def _chk(name, t, dtypes, shape):
     if tuple(t.shape) != tuple(shape):
         raise ValueError("%s has shape %s, expected %s" % (name, tuple(t.shape), tuple(shape)))
     return t
-
-
-def _call(name, like, *args):
-    with _on_device(like):
-        rc = _fn(name)(*args, _stream(like))
-    _lib.check(rc, name)
 
 
 def preprocess_u8(img, table, out):

@@ -20,9 +20,11 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import ops2d
 from ._lib import DecnetHipError, UNSUPPORTED
 from .ops import spamatvar_forward, spamatvar_forward_bits
-from .stage0 import CachesWeights, CostRegNetNoDown, Stage0, drop_weight_caches, source_hold, source_key  # noqa: F401
+from .stage0 import (CachesWeights, CostRegNetNoDown, Stage0, cache_attrs, drop_weight_caches, fold_bn, fold_none,  # noqa: F401
+                     source_hold, source_key)
 
 
 # bench.py's end-to-end accounting: a list that every Unit launch appends (kernel family, algorithmic flops, algorithmic
@@ -49,11 +51,49 @@ def _tally(unit, kind, x):
                   "bytes": 4.0 * B * (cin * H * W + co * Ho * Wo)})
 
 
+# ---- which launches the HIP trunk takes: the switches (read per call), the gate, the layer shapes ----------------------------
+def conv2d_switch():
+    """DECNET_CONV2D: "hip" (the default) or anything else for the library route everywhere."""
+    return os.environ.get("DECNET_CONV2D", "hip") == "hip"
+
+
+def mfma_switch():
+    """DECNET_CONV2D_MFMA=0 keeps the matrix-core kernels out of the trunk."""
+    return os.environ.get("DECNET_CONV2D_MFMA", "1") == "1"
+
+
+def spamat_bits_switch():
+    return os.environ.get("DECNET_SPAMAT_BITS", "1") == "1"
+
+
+def hip_gate(t, training=False, fp32=True, switch=True):
+    """The HIP trunk may take this tensor: on the GPU, no autograd, not `training` (the module's flag, where the site has
+    one), and -- terms a site can leave out or check elsewhere -- float32 and DECNET_CONV2D=hip."""
+    return (not training and t.is_cuda and not torch.is_grad_enabled() and (not fp32 or t.dtype == torch.float32) and
+            (not switch or conv2d_switch()))
+
+
+def _same_padded(c):
+    """Conv2d k 1 or 3, stride 1, zero padding that keeps the size at its (square) dilation."""
+    return (isinstance(c, nn.Conv2d) and c.kernel_size in ((1, 1), (3, 3)) and c.stride == (1, 1) and
+            c.dilation[0] == c.dilation[1] and c.padding == (c.dilation[0] * (c.kernel_size[0] // 2),) * 2 and
+            c.groups == 1 and c.padding_mode == "zeros")
+
+
+def _k3s3p1(c):
+    return (isinstance(c, nn.Conv2d) and c.kernel_size == (3, 3) and c.stride == (3, 3) and c.padding == (1, 1) and
+            c.dilation == (1, 1) and c.groups == 1 and c.padding_mode == "zeros")
+
+
+def _deconv_k3s3(c):
+    return (isinstance(c, nn.ConvTranspose2d) and c.kernel_size == (3, 3) and c.stride == (3, 3) and c.padding == (0, 0) and
+            c.output_padding == (0, 0) and c.dilation == (1, 1) and c.groups == 1)
+
+
 class Unit(CachesWeights, nn.Module):
     """conv / transposed conv -> optional BatchNorm2d -> optional ReLU; attributes ``conv`` and
     ``bn`` as in the reference's Conv2dUnit / Deconv2dUnit (submodule.py:15-87)."""
-    _CACHE_ATTRS = ("_fold", "_fold_key", "_fold_src", "_mfold", "_mfold_key", "_mfold_src",
-                    "_tfold", "_tfold_key", "_tfold_src")
+    _CACHE_ATTRS = cache_attrs("_fold", "_mfold", "_tfold")
 
     def __init__(self, cin, cout, k, stride=1, pad=0, dil=1, relu=True, bn=True, momentum=0.1,
                  transposed=False):
@@ -67,290 +107,136 @@ class Unit(CachesWeights, nn.Module):
 
     # ---- fused HIP path for the full-resolution few-channel layers (csrc/conv2d_small.hip) ----
     def _hip_kind(self, x):
-        """"conv" / "deconv" / "conv_s3" when this unit, in eval mode on the GPU, is one the
-        small-channel kernels cover (they pay off where the tensors are large: >= 64 k pixels per
-        image); else None.  x: a tensor, or a tuple of tensors standing for their channel concatenation."""
+        """"conv" / "deconv" / "conv_s3" / "mfma" / "mfma_s3" / "mfma_deconv" when this unit, in eval mode on the GPU, is one
+        the HIP kernels cover; else None.  x: a tensor, or a tuple of tensors standing for their channel concatenation."""
+        parts = None
         if isinstance(x, (tuple, list)):
-            if (len(x) > 6 or any(t.shape[0] != x[0].shape[0] or t.shape[2:] != x[0].shape[2:] or t.dtype != x[0].dtype
-                                  or t.device != x[0].device for t in x)):
+            parts, x0 = len(x), x[0]
+            if any(t.shape[0] != x0.shape[0] or t.shape[2:] != x0.shape[2:] or t.dtype != x0.dtype or
+                   t.device != x0.device for t in x):
                 return None
-            kind = self._hip_kind(x[0])
-            return kind if kind in ("conv", "mfma") else None
-        if self.training or not x.is_cuda or x.dtype != torch.float32 or torch.is_grad_enabled():
+            x = x0
+        if not hip_gate(x, self.training, switch=False):
             return None
-        if os.environ.get("DECNET_CONV2D", "hip") != "hip":
-            return None
-        c = self.conv
-        # many channels: the bf16x3 matrix-core kernel (csrc/conv2d_mfma.hip) where the image gives it enough
-        # workgroups (>= 4096 pixels, e.g. the 60 x 108 level; at 20 x 36 the library's kernels win)
-        # (round 3: also 9..23 outputs from >= 16 inputs.  The 20 x 36 level stays on the library: measured with the
-        # pixel threshold at 512, 649 -> 81 takes 0.265 ms here against 0.107 ms, the 864 / 432 -> 216 1 x 1 layers
-        # 0.131 / 0.081 against 0.053 / 0.042 -- 144 workgroups of a K = 5841 reduction each do not fill 256 CUs)
-        if (isinstance(c, nn.Conv2d) and
-                (c.out_channels >= 9 or c.in_channels >= 48) and
-                c.in_channels >= 16 and c.kernel_size in ((1, 1), (3, 3)) and
-                c.stride == (1, 1) and c.dilation[0] == c.dilation[1] and c.groups == 1 and c.padding_mode == "zeros" and
-                c.padding == (c.dilation[0] * (c.kernel_size[0] // 2),) * 2 and
-                x.shape[-1] * x.shape[-2] >= 4096 and
-                c.dilation[0] <= 4 and os.environ.get("DECNET_CONV2D_MFMA", "1") == "1"):
-            return "mfma"
-        # Conv2d k 3, stride 3, padding 1 with more than 24 outputs: space-to-depth + the same kernel as a 1 x 1 convolution
-        if (isinstance(c, nn.Conv2d) and c.kernel_size == (3, 3) and c.stride == (3, 3) and c.padding == (1, 1) and
-                c.dilation == (1, 1) and c.groups == 1 and c.padding_mode == "zeros" and c.out_channels > 24 and
-                c.in_channels >= 8 and x.shape[-1] * x.shape[-2] >= 4608 and
-                os.environ.get("DECNET_CONV2D_MFMA", "1") == "1"):
-            return "mfma_s3"
-        # transposed convolution k = 3, stride 3 with more than 8 output channels: the same kernel, as a 1 x 1 convolution
-        # to 9 Cout channels with a pixel-shuffle store
-        if (isinstance(c, nn.ConvTranspose2d) and (c.out_channels > 8 or c.in_channels >= 64) and c.in_channels >= 16 and
-                c.kernel_size == (3, 3) and
-                c.stride == (3, 3) and c.padding == (0, 0) and c.output_padding == (0, 0) and c.dilation == (1, 1) and
-                c.groups == 1 and x.shape[-1] * x.shape[-2] >= 512 and
-                os.environ.get("DECNET_CONV2D_MFMA", "1") == "1"):
-            return "mfma_deconv"
+        return self._route(x.shape[0], x.shape[-2], x.shape[-1], parts)
+
+    def _route(self, B, H, W, parts=None):
+        """The table behind _hip_kind, a function of the layer, the input size, the number of concatenated parts (None:
+        one tensor) and the two switches alone: no tensor, no GPU.  (No threshold depends on B today.)"""
+        c, hw = self.conv, H * W
+        ci, co, tr = c.in_channels, c.out_channels, isinstance(c, nn.ConvTranspose2d)
+        if not conv2d_switch() or (parts is not None and (parts > 6 or not _same_padded(c))):  # (the `cat` entries are
+            return None                                                                        # "conv"'s and "mfma"'s)
+        if mfma_switch():
+            # many channels: the bf16x3 matrix-core kernel (csrc/conv2d_mfma.hip) where the image gives it enough
+            # workgroups (>= 4096 pixels, e.g. the 60 x 108 level; at 20 x 36 the library's kernels win)
+            # (round 3: also 9..23 outputs from >= 16 inputs.  The 20 x 36 level stays on the library: measured with the
+            # pixel threshold at 512, 649 -> 81 takes 0.265 ms here against 0.107 ms, the 864 / 432 -> 216 1 x 1 layers
+            # 0.131 / 0.081 against 0.053 / 0.042 -- 144 workgroups of a K = 5841 reduction each do not fill 256 CUs)
+            if (co >= 9 or ci >= 48) and ci >= 16 and hw >= 4096 and c.dilation[0] <= 4 and _same_padded(c):
+                return "mfma"
+            # Conv2d k 3, stride 3, padding 1 with more than 24 outputs: space-to-depth + the same kernel as a 1 x 1 convolution
+            if co > 24 and ci >= 8 and hw >= 4608 and _k3s3p1(c):
+                return "mfma_s3"
+            # transposed convolution k = 3, stride 3 with more than 8 output channels: the same kernel, as a 1 x 1
+            # convolution to 9 Cout channels with a pixel-shuffle store
+            if tr and (co > 8 or ci >= 64) and ci >= 16 and hw >= 512 and _deconv_k3s3(c):
+                return "mfma_deconv"
         # the few-channel kernels at every size (at 60 x 108 and 20 x 36 they do not fill the chip, but one launch
         # replaces the library's convolution + layout transposes + bias / ReLU passes)
-        up = 9 if isinstance(c, nn.ConvTranspose2d) else 1
-        if x.shape[-1] * x.shape[-2] * up < 256:
+        if hw * (9 if tr else 1) < 256:
             return None
-        if (isinstance(c, nn.Conv2d) and c.kernel_size == (3, 3) and c.stride == (3, 3) and c.padding == (1, 1) and
-                c.dilation == (1, 1) and c.groups == 1 and c.padding_mode == "zeros" and c.out_channels <= 24):
+        if co <= 24 and c.stride == (3, 3) and _k3s3p1(c):
             return "conv_s3"
-        tr = isinstance(c, nn.ConvTranspose2d)
         # 9..24 output channels: only where the library is slow (dilated taps) or the input is thin
-        if c.out_channels > (8 if tr else 24) or (c.out_channels > 8 and c.dilation[0] == 1 and c.in_channels > 12):
+        if co > (8 if tr else 24) or (co > 8 and c.dilation[0] == 1 and ci > 12):
             return None
-        if isinstance(c, nn.ConvTranspose2d):
-            ok = (c.kernel_size == (3, 3) and c.stride == (3, 3) and c.padding == (0, 0) and
-                  c.output_padding == (0, 0) and c.dilation == (1, 1) and c.groups == 1)
-            return "deconv" if ok else None
-        k = c.kernel_size[0]
-        ok = (c.kernel_size in ((1, 1), (3, 3)) and c.stride == (1, 1) and c.dilation[0] == c.dilation[1] and
-              c.padding == (c.dilation[0] * (k // 2),) * 2 and c.groups == 1 and c.padding_mode == "zeros")
-        return "conv" if ok else None
+        if tr:
+            return "deconv" if _deconv_k3s3(c) else None
+        return "conv" if _same_padded(c) else None
 
     def _sources(self):
         c, bn = self.conv, self.bn
         return [c.weight] + ([bn.weight, bn.bias, bn.running_mean, bn.running_var] if bn is not None else
                              ([c.bias] if c.bias is not None else []))
 
+    def _scale_shift(self):
+        scale, shift = fold_bn(self.bn) if self.bn is not None else fold_none(self.conv)
+        return scale.contiguous(), shift.contiguous()
+
     def _folded(self, neg_last=False):
         """Per-channel scale / shift of the eval-mode BatchNorm (or 1 / bias), cached per weight version (stage0.source_key:
         a write through ``.data`` after the first forward needs ``drop_weight_caches``).
         neg_last: the weights of the last input channel negated (a caller that feeds -x passes x instead)."""
-        c, bn = self.conv, self.bn
-        ts = self._sources()
-        key = source_key(ts, bn.eps if bn is not None else None, bool(neg_last))
-        if getattr(self, "_fold_key", None) != key:
-            with torch.no_grad():
-                co = c.out_channels
-                if bn is not None:
-                    scale = bn.weight.float() / torch.sqrt(bn.running_var.float() + bn.eps)
-                    shift = bn.bias.float() - bn.running_mean.float() * scale
-                else:
-                    scale = torch.ones(co, device=c.weight.device)
-                    shift = c.bias.float() if c.bias is not None else torch.zeros(co, device=c.weight.device)
-                from . import _lib
-                L = _lib.lib()
-                tr = 1 if isinstance(c, nn.ConvTranspose2d) else 0
-                w = c.weight.detach().float().contiguous()
-                if neg_last:
-                    w = w.clone()
-                    w[:, -1] = -w[:, -1]
-                k = c.kernel_size[0]
-                wp = torch.empty(L.decnet_conv2d_packed_floats(c.in_channels, co, k, tr), dtype=torch.float32,
-                                 device=w.device)
-                with torch.cuda.device(w.device):
-                    _lib.check(L.decnet_conv2d_pack_weight(w.data_ptr(), wp.data_ptr(), c.in_channels, co, k, tr,
-                                                           torch.cuda.current_stream(w.device).cuda_stream),
-                               "decnet_conv2d_pack_weight")
-                self._fold = (wp, scale.contiguous(), shift.contiguous())
-            self._fold_key, self._fold_src = key, source_hold(ts)
-        return self._fold
+        def build():
+            w = self.conv.weight.detach().float().contiguous()
+            if neg_last:
+                w = w.clone()
+                w[:, -1] = -w[:, -1]
+            return (ops2d.conv2d_pack_weight(w, isinstance(self.conv, nn.ConvTranspose2d)),) + self._scale_shift()
+        return self._cached("_fold", self._sources(), (self.bn.eps if self.bn is not None else None, bool(neg_last)), build)
 
     def _folded_mfma(self):
         """Weights split into bf16 terms in the operand layout of csrc/conv2d_mfma.hip + folded BN, cached per version
         (stage0.source_key: a write through ``.data`` after the first forward needs ``drop_weight_caches``)."""
-        c, bn = self.conv, self.bn
-        ts = self._sources()
-        key = source_key(ts, bn.eps if bn is not None else None)
-        if getattr(self, "_mfold_key", None) != key:
-            from . import _lib
-            L = _lib.lib()
-            with torch.no_grad():
-                co, ci, k = c.out_channels, c.in_channels, c.kernel_size[0]
-                if bn is not None:
-                    scale = bn.weight.float() / torch.sqrt(bn.running_var.float() + bn.eps)
-                    shift = bn.bias.float() - bn.running_mean.float() * scale
-                else:
-                    scale = torch.ones(co, device=c.weight.device)
-                    shift = c.bias.float() if c.bias is not None else torch.zeros(co, device=c.weight.device)
-                w = c.weight.detach().float().contiguous()
-                st = torch.cuda.current_stream(w.device).cuda_stream
-                if isinstance(c, nn.Conv2d) and c.stride == (3, 3):      # stride-3: [Cout, Cin, 3, 3] read as [Cout, 9 Cin]
-                    wp = torch.empty(L.decnet_conv2d_mfma_packed_bytes(9 * ci, co, 1), dtype=torch.uint8, device=w.device)
-                    with torch.cuda.device(w.device):
-                        _lib.check(L.decnet_conv2d_mfma_pack_weight(w.data_ptr(), wp.data_ptr(), 9 * ci, co, 1, st),
-                                   "decnet_conv2d_mfma_pack_weight")
-                elif isinstance(c, nn.ConvTranspose2d):
-                    wp = torch.empty(L.decnet_deconv2d_mfma_packed_bytes(ci, co), dtype=torch.uint8, device=w.device)
-                    with torch.cuda.device(w.device):
-                        _lib.check(L.decnet_deconv2d_mfma_pack_weight(w.data_ptr(), wp.data_ptr(), ci, co, st),
-                                   "decnet_deconv2d_mfma_pack_weight")
-                else:
-                    wp = torch.empty(L.decnet_conv2d_mfma_packed_bytes(ci, co, k), dtype=torch.uint8, device=w.device)
-                    with torch.cuda.device(w.device):
-                        _lib.check(L.decnet_conv2d_mfma_pack_weight(w.data_ptr(), wp.data_ptr(), ci, co, k, st),
-                                   "decnet_conv2d_mfma_pack_weight")
-                self._mfold = (wp, scale.contiguous(), shift.contiguous())
-            self._mfold_key, self._mfold_src = key, source_hold(ts)
-        return self._mfold
-
-    def _forward_mfma(self, x):
-        import ctypes
-        from . import _lib
-        from .ops import _stream
-        wp, scale, shift = self._folded_mfma()
-        xs = [t.contiguous() for t in (x if isinstance(x, (tuple, list)) else (x,))]
-        B, _, H, W = xs[0].shape
-        c = self.conv
-        assert sum(t.shape[1] for t in xs) == c.in_channels
-        y = torch.empty((B, c.out_channels, H, W), dtype=torch.float32, device=xs[0].device)
-        ptrs = (ctypes.c_void_p * len(xs))(*[t.data_ptr() for t in xs])
-        cins = (ctypes.c_int * len(xs))(*[int(t.shape[1]) for t in xs])
-        with torch.cuda.device(y.device):
-            rc = _lib.lib().decnet_conv2d_mfma_cat_bn_act(ptrs, cins, len(xs), wp.data_ptr(), scale.data_ptr(),
-                                                          shift.data_ptr(), y.data_ptr(), B, c.out_channels, H, W,
-                                                          c.kernel_size[0], c.dilation[0], 1 if self.relu else 0,
-                                                          _stream(y))
-        _lib.check(rc, "decnet_conv2d_mfma_cat_bn_act")
-        return y
-
-    def _forward_mfma_s3(self, x):
-        """Conv2d k 3, stride 3, padding 1: decnet_s2d3_pad1 + the matrix-core kernel as a 1 x 1 convolution."""
-        import ctypes
-        from . import _lib
-        from .ops import _stream
-        wp, scale, shift = self._folded_mfma()
-        x = x.contiguous()
-        B, Cin, H, W = x.shape
-        c = self.conv
-        Ho, Wo = (H - 1) // 3 + 1, (W - 1) // 3 + 1
-        t = torch.empty((B, 9 * Cin, Ho, Wo), dtype=torch.float32, device=x.device)
-        y = torch.empty((B, c.out_channels, Ho, Wo), dtype=torch.float32, device=x.device)
-        L = _lib.lib()
-        with torch.cuda.device(x.device):
-            _lib.check(L.decnet_s2d3_pad1(x.data_ptr(), t.data_ptr(), B, Cin, H, W, _stream(x)), "decnet_s2d3_pad1")
-            ptrs = (ctypes.c_void_p * 1)(t.data_ptr())
-            cins = (ctypes.c_int * 1)(9 * Cin)
-            rc = L.decnet_conv2d_mfma_cat_bn_act(ptrs, cins, 1, wp.data_ptr(), scale.data_ptr(), shift.data_ptr(),
-                                                 y.data_ptr(), B, c.out_channels, Ho, Wo, 1, 1, 1 if self.relu else 0,
-                                                 _stream(y))
-        _lib.check(rc, "decnet_conv2d_mfma_cat_bn_act")
-        return y
-
-    def _forward_mfma_deconv(self, x):
-        from . import _lib
-        from .ops import _stream
-        wp, scale, shift = self._folded_mfma()
-        x = x.contiguous()
-        B, Cin, H, W = x.shape
-        c = self.conv
-        y = torch.empty((B, c.out_channels, 3 * H, 3 * W), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            rc = _lib.lib().decnet_deconv2d_mfma_k3s3_bn_act(x.data_ptr(), wp.data_ptr(), scale.data_ptr(), shift.data_ptr(),
-                                                             y.data_ptr(), B, Cin, c.out_channels, H, W,
-                                                             1 if self.relu else 0, _stream(x))
-        _lib.check(rc, "decnet_deconv2d_mfma_k3s3_bn_act")
-        return y
-
-    def _forward_hip(self, x, kind, out=None, epi=0, ea=None, eb=None, neg_last=False):
-        """out: write into this [B,Cout,H,W] buffer (kind "conv"); epi / ea / eb: decnet_conv2d_cat_epilogue's fused tail
-        of a single-output layer; neg_last: see _folded."""
-        if TALLY is not None:
-            n_tally = len(TALLY)
-            _tally(self, kind, x)
-            try:
-                return self._forward_hip_kind(x, kind, out, epi, ea, eb, neg_last)
-            except DecnetHipError:                       # forward() falls back to the library path and tallies THAT
-                del TALLY[n_tally:]
-                raise
-        return self._forward_hip_kind(x, kind, out, epi, ea, eb, neg_last)
-
-    def _forward_hip_kind(self, x, kind, out, epi, ea, eb, neg_last):
-        if kind == "mfma":
-            return self._forward_mfma(x)
-        if kind == "mfma_deconv":
-            return self._forward_mfma_deconv(x)
-        if kind == "mfma_s3":
-            return self._forward_mfma_s3(x)
-        from . import _lib
-        from .ops import _stream
-        w, scale, shift = self._folded(neg_last)
-        if isinstance(x, (tuple, list)) or epi:         # concatenated input, never materialised
-            import ctypes
-            xs = [t.contiguous() for t in (x if isinstance(x, (tuple, list)) else (x,))]
-            B, _, H, W = xs[0].shape
-            Co = self.conv.out_channels
-            assert sum(t.shape[1] for t in xs) == self.conv.in_channels
-            y = out if out is not None else torch.empty((B, Co, H, W), dtype=torch.float32, device=xs[0].device)
-            ptrs = (ctypes.c_void_p * len(xs))(*[t.data_ptr() for t in xs])
-            cins = (ctypes.c_int * len(xs))(*[int(t.shape[1]) for t in xs])
-            with torch.cuda.device(y.device):
-                if epi:
-                    assert Co == 1 and ea.is_contiguous() and (eb is None or eb.is_contiguous())
-                    rc = _lib.lib().decnet_conv2d_cat_epilogue(ptrs, cins, len(xs), w.data_ptr(), scale.data_ptr(),
-                                                               shift.data_ptr(), y.data_ptr(), B, H, W,
-                                                               self.conv.kernel_size[0], self.conv.dilation[0],
-                                                               1 if self.relu else 0, int(epi), ea.data_ptr(),
-                                                               eb.data_ptr() if eb is not None else None, _stream(y))
-                    _lib.check(rc, "decnet_conv2d_cat_epilogue")
-                    return y
-                rc = _lib.lib().decnet_conv2d_cat_bn_act(ptrs, cins, len(xs), w.data_ptr(), scale.data_ptr(),
-                                                         shift.data_ptr(), y.data_ptr(), B, Co, H, W,
-                                                         self.conv.kernel_size[0], self.conv.dilation[0],
-                                                         1 if self.relu else 0, _stream(y))
-            _lib.check(rc, "decnet_conv2d_cat_bn_act")
-            return y
-        x = x.contiguous()
-        B, Cin, H, W = x.shape
-        Co = self.conv.out_channels
-        L = _lib.lib()
-        with torch.cuda.device(x.device):
-            if kind == "conv_s3":
-                y = torch.empty((B, Co, (H - 1) // 3 + 1, (W - 1) // 3 + 1), dtype=torch.float32, device=x.device)
-                rc = L.decnet_conv2d_k3s3_bn_act(x.data_ptr(), w.data_ptr(), scale.data_ptr(), shift.data_ptr(),
-                                                 y.data_ptr(), B, Cin, Co, H, W, 1 if self.relu else 0, _stream(x))
-            elif kind == "deconv":
-                y = torch.empty((B, Co, 3 * H, 3 * W), dtype=torch.float32, device=x.device)
-                rc = L.decnet_deconv2d_k3s3_bn_act(x.data_ptr(), w.data_ptr(), scale.data_ptr(), shift.data_ptr(),
-                                                   y.data_ptr(), B, Cin, Co, H, W, 1 if self.relu else 0,
-                                                   _stream(x))
-            else:
-                y = out if out is not None else torch.empty((B, Co, H, W), dtype=torch.float32, device=x.device)
-                assert y.is_contiguous()
-                rc = L.decnet_conv2d_bn_act(x.data_ptr(), w.data_ptr(), scale.data_ptr(), shift.data_ptr(),
-                                            y.data_ptr(), B, Cin, Co, H, W, self.conv.kernel_size[0],
-                                            self.conv.dilation[0], 1 if self.relu else 0, _stream(x))
-        _lib.check(rc, {"conv": "decnet_conv2d_bn_act", "deconv": "decnet_deconv2d_k3s3_bn_act",
-                        "conv_s3": "decnet_conv2d_k3s3_bn_act"}[kind])
-        return y
+        def build():
+            c = self.conv
+            w = c.weight.detach().float().contiguous()
+            if isinstance(c, nn.ConvTranspose2d):
+                return (ops2d.deconv2d_mfma_pack_weight(w),) + self._scale_shift()
+            s3 = c.stride == (3, 3)                                 # stride-3: [Cout, Cin, 3, 3] read as [Cout, 9 Cin]
+            return (ops2d.conv2d_mfma_pack_weight(w, 9 * c.in_channels, 1) if s3 else
+                    ops2d.conv2d_mfma_pack_weight(w, c.in_channels, c.kernel_size[0]),) + self._scale_shift()
+        return self._cached("_mfold", self._sources(), (self.bn.eps if self.bn is not None else None,), build)
 
     def _folded_torch(self):
         """Eval-mode BatchNorm folded into the convolution itself (w * scale per output channel, bias =
         shift) for the layers that stay on MIOpen: one kernel instead of conv + batch-norm.  Cached per version
         (stage0.source_key: a write through ``.data`` after the first forward needs ``drop_weight_caches``)."""
-        c, bn = self.conv, self.bn
-        ts = self._sources()
-        key = source_key(ts, bn.eps)
-        if getattr(self, "_tfold_key", None) != key:
-            with torch.no_grad():
-                scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)
-                shift = bn.bias - bn.running_mean * scale
-                shape = (1, -1, 1, 1) if isinstance(c, nn.ConvTranspose2d) else (-1, 1, 1, 1)
-                self._tfold = ((c.weight * scale.view(shape)).contiguous(), shift.contiguous())
-            self._tfold_key, self._tfold_src = key, source_hold(ts)
-        return self._tfold
+        def build():
+            scale, shift = fold_bn(self.bn, fp32=False)
+            shape = (1, -1, 1, 1) if isinstance(self.conv, nn.ConvTranspose2d) else (-1, 1, 1, 1)
+            return (self.conv.weight * scale.view(shape)).contiguous(), shift.contiguous()
+        return self._cached("_tfold", self._sources(), (self.bn.eps,), build)
+
+    def _forward_mfma(self, x):
+        c, xs = self.conv, [t.contiguous() for t in (x if isinstance(x, (tuple, list)) else (x,))]
+        return ops2d.conv2d_mfma_cat_bn_act(xs, *self._folded_mfma(), c.in_channels, c.kernel_size[0], c.dilation[0],
+                                            1 if self.relu else 0)
+
+    def _forward_hip(self, x, kind, out=None, epi=0, ea=None, eb=None, neg_last=False):
+        """out: write into this [B,Cout,H,W] buffer (kind "conv"); epi / ea / eb: decnet_conv2d_cat_epilogue's fused tail
+        of a single-output layer; neg_last: see _folded."""
+        if TALLY is None:
+            return self._forward_hip_kind(x, kind, out, epi, ea, eb, neg_last)
+        n_tally = len(TALLY)
+        _tally(self, kind, x)
+        try:
+            return self._forward_hip_kind(x, kind, out, epi, ea, eb, neg_last)
+        except DecnetHipError:                           # forward() falls back to the library path and tallies THAT
+            del TALLY[n_tally:]
+            raise
+
+    def _forward_hip_kind(self, x, kind, out, epi, ea, eb, neg_last):
+        c, relu = self.conv, 1 if self.relu else 0
+        ci, k, dil = c.in_channels, c.kernel_size[0], c.dilation[0]
+        if kind == "mfma":
+            return self._forward_mfma(x)
+        if kind == "mfma_deconv":
+            return ops2d.deconv2d_mfma_k3s3_bn_act(x.contiguous(), *self._folded_mfma(), ci, relu)
+        if kind == "mfma_s3":       # Conv2d k 3, stride 3, padding 1: decnet_s2d3_pad1 + the matrix-core kernel as a 1 x 1 conv
+            return ops2d.conv2d_mfma_cat_bn_act([ops2d.s2d3_pad1(x.contiguous())], *self._folded_mfma(), 9 * ci, 1, 1, relu)
+        wss = self._folded(neg_last)
+        if isinstance(x, (tuple, list)) or epi:         # concatenated input, never materialised
+            xs = [t.contiguous() for t in (x if isinstance(x, (tuple, list)) else (x,))]
+            if epi:
+                return ops2d.conv2d_cat_epilogue(xs, *wss, ci, k, dil, relu, epi, ea, eb, out=out)
+            return ops2d.conv2d_cat_bn_act(xs, *wss, ci, k, dil, relu, out=out)
+        if kind == "conv_s3":
+            return ops2d.conv2d_k3s3_bn_act(x.contiguous(), *wss, ci, relu)
+        if kind == "deconv":
+            return ops2d.deconv2d_k3s3_bn_act(x.contiguous(), *wss, ci, relu)
+        return ops2d.conv2d_bn_act(x.contiguous(), *wss, ci, k, dil, relu, out=out)
 
     def forward(self, x):
         kind = self._hip_kind(x)
@@ -364,7 +250,7 @@ class Unit(CachesWeights, nn.Module):
             _tally(self, "library", x)
         if isinstance(x, (tuple, list)):
             x = torch.cat(tuple(x), 1)
-        if self.bn is not None and not self.training and not torch.is_grad_enabled() and x.is_cuda:
+        if self.bn is not None and hip_gate(x, self.training, fp32=False, switch=False):
             w, b = self._folded_torch()
             c = self.conv
             if isinstance(c, nn.ConvTranspose2d):
@@ -372,15 +258,8 @@ class Unit(CachesWeights, nn.Module):
             else:
                 x = F.conv2d(x, w, None, c.stride, c.padding, c.dilation, c.groups)
             # bias + ReLU in one in-place pass (the library would add the bias in a kernel of its own)
-            from . import _lib
-            from .ops import _stream
-            B, Co, H, W = x.shape
-            if x.is_contiguous() and B * Co <= 65535:
-                with torch.cuda.device(x.device):
-                    _lib.check(_lib.lib().decnet_bias_act_inplace(x.data_ptr(), b.data_ptr(), B, Co, H, W,
-                                                                  1 if self.relu else 0, _stream(x)),
-                               "decnet_bias_act_inplace")
-                return x
+            if x.is_contiguous() and x.dtype == torch.float32 and x.shape[0] * x.shape[1] <= 65535:
+                return ops2d.bias_act_inplace(x, b, 1 if self.relu else 0)
             x = x + b.view(1, -1, 1, 1)
             return torch.relu_(x) if self.relu else x
         x = self.conv(x)
@@ -429,7 +308,7 @@ class UpBlock(nn.Module):
 
 class ASPP(CachesWeights, nn.Module):
     """submodule.py:225-241: a 1x1 branch and three dilated 3x3 branches, concatenated."""
-    _CACHE_ATTRS = ("_pk", "_pk_key", "_pk_src")
+    _CACHE_ATTRS = cache_attrs("_pk")
 
     def __init__(self, cin, cout, rates):
         super().__init__()
@@ -440,78 +319,46 @@ class ASPP(CachesWeights, nn.Module):
 
     # ---- fused path (csrc/tapconv.hip): one V, one batched per-tap GEMM, one gather for all branches ----
     def _hip_ok(self, x):
-        if (self.training or not x.is_cuda or x.dtype != torch.float32 or torch.is_grad_enabled() or
-                os.environ.get("DECNET_CONV2D", "hip") != "hip"):
-            return False
+        return hip_gate(x, self.training, switch=False) and self._fusable(x.shape[-2], x.shape[-1])
+
+    def _fusable(self, H, W):
+        """The block's shape is one the tap-conv kernels take (a function of the layers, the image size and DECNET_CONV2D
+        alone): up to four same-padded BN + ReLU branches of one Cin -> Cout, Cin % 4 == 0, Cout <= 224, <= 16384 pixels."""
         units = list(self.stages.children())
         c0 = units[0].conv
-        if len(units) > 4 or c0.in_channels % 4 or c0.out_channels > 224 or x.shape[-1] * x.shape[-2] > 16384:
+        if not conv2d_switch() or len(units) > 4 or c0.in_channels % 4 or c0.out_channels > 224 or H * W > 16384:
             return False
-        for u in units:
-            c = u.conv
-            k = c.kernel_size[0]
-            if (not isinstance(c, nn.Conv2d) or u.bn is None or not u.relu or c.kernel_size not in ((1, 1), (3, 3)) or
-                    c.stride != (1, 1) or c.dilation[0] != c.dilation[1] or c.groups != 1 or
-                    c.padding != (c.dilation[0] * (k // 2),) * 2 or c.out_channels != c0.out_channels or
-                    c.in_channels != c0.in_channels):
-                return False
-        return True
+        return all(_same_padded(u.conv) and u.bn is not None and u.relu and u.conv.out_channels == c0.out_channels and
+                   u.conv.in_channels == c0.in_channels for u in units)
 
     def _packed(self):
         """All branches' weights in the per-tap GEMM's layout + folded BN, cached per version (stage0.source_key: a
         write through ``.data`` after the first forward needs ``drop_weight_caches``)."""
-        from . import _lib
         units = list(self.stages.children())
         ts = [t for u in units for t in (u.conv.weight, u.bn.weight, u.bn.bias, u.bn.running_mean, u.bn.running_var)]
-        key = source_key(ts, *[u.bn.eps for u in units])
-        if getattr(self, "_pk_key", None) != key:
-            L = _lib.lib()
-            dev = units[0].conv.weight.device
+
+        def build():
             ci, co = units[0].conv.in_channels, units[0].conv.out_channels
             ks = [u.conv.kernel_size[0] for u in units]
             tap0 = [sum(k * k for k in ks[:i]) for i in range(len(ks))]
             ntaps = sum(k * k for k in ks)
-            with torch.no_grad(), torch.cuda.device(dev):
-                st = torch.cuda.current_stream(dev).cuda_stream
-                u_all = torch.empty(L.decnet_tapconv_weight_floats(ci, ntaps), dtype=torch.float32, device=dev)
-                scale, shift = [], []
-                for u, k, t0 in zip(units, ks, tap0):
-                    w = u.conv.weight.detach().float().contiguous()
-                    _lib.check(L.decnet_tapconv_pack_weight(w.data_ptr(), u_all.data_ptr(), co, ci, k, t0, st),
-                               "decnet_tapconv_pack_weight")
-                    sc = u.bn.weight.float() / torch.sqrt(u.bn.running_var.float() + u.bn.eps)
-                    scale.append(sc)
-                    shift.append(u.bn.bias.float() - u.bn.running_mean.float() * sc)
-                _lib.check(L.decnet_tapconv_split_weight(u_all.data_ptr(), ci, ntaps, st), "decnet_tapconv_split_weight")
-                torch.cuda.current_stream(dev).synchronize()          # w temporaries may go now
-            self._pk = dict(u=u_all, scale=torch.cat(scale).contiguous(), shift=torch.cat(shift).contiguous(),
-                            ks=ks, tap0=tap0, ntaps=ntaps, dil=[u.conv.dilation[0] for u in units])
-            self._pk_key, self._pk_src = key, source_hold(ts)
-        return self._pk
+            u_all = torch.empty(ops2d.size("tapconv_weight_floats", ci, ntaps), dtype=torch.float32,
+                                device=units[0].conv.weight.device)
+            for u, t0 in zip(units, tap0):
+                ops2d.tapconv_pack_weight(u.conv.weight.detach().float().contiguous(), u_all, t0)
+            ops2d.tapconv_split_weight(u_all, ci, ntaps)
+            torch.cuda.current_stream(u_all.device).synchronize()      # the weights' fp32 temporaries may go now
+            scale, shift = zip(*[fold_bn(u.bn) for u in units])
+            return dict(u=u_all, scale=torch.cat(scale).contiguous(), shift=torch.cat(shift).contiguous(), ks=ks, tap0=tap0,
+                        ntaps=ntaps, dil=[u.conv.dilation[0] for u in units], co=co)
+        return self._cached("_pk", ts, [u.bn.eps for u in units], build)
 
     def _forward_hip(self, x):
-        import ctypes
-        from . import _lib
-        from .ops import _stream
         pk = self._packed()
-        L = _lib.lib()
         x = x.contiguous()
         B, Ci, H, W = x.shape
-        Co, nb = list(self.stages.children())[0].conv.out_channels, len(pk["ks"])
-        P = B * H * W
-        V = torch.empty(L.decnet_tapconv_chunk_floats(B, Ci, H, W), dtype=torch.float32, device=x.device)
-        T = torch.empty(pk["ntaps"] * ((Co + 15) // 16) * 16 * P, dtype=torch.float32, device=x.device)
-        y = torch.empty((B, nb * Co, H, W), dtype=torch.float32, device=x.device)
-        arr = lambda v: (ctypes.c_int * len(v))(*v)
-        with torch.cuda.device(x.device):
-            st = _stream(x)
-            _lib.check(L.decnet_tapconv_to_chunks(x.data_ptr(), V.data_ptr(), B, Ci, H, W, st), "decnet_tapconv_to_chunks")
-            _lib.check(L.decnet_tap_gemm(V.data_ptr(), pk["u"].data_ptr(), T.data_ptr(), P, Ci, Co, pk["ntaps"], 1, st),
-                       "decnet_tap_gemm")
-            _lib.check(L.decnet_tapconv_gather(T.data_ptr(), pk["scale"].data_ptr(), pk["shift"].data_ptr(),
-                                               y.data_ptr(), B, Co, H, W, nb, arr(pk["tap0"]), arr(pk["ks"]),
-                                               arr(pk["dil"]), 1, st), "decnet_tapconv_gather")
-        return y
+        T = ops2d.tap_gemm(ops2d.tapconv_to_chunks(x), pk["u"], B * H * W, Ci, pk["co"], pk["ntaps"], 1)
+        return ops2d.tapconv_gather(T, pk["scale"], pk["shift"], B, pk["co"], H, W, pk["tap0"], pk["ks"], pk["dil"], 1)
 
     def forward(self, x):
         if self._hip_ok(x):
@@ -573,7 +420,7 @@ class FeatExtNetChannelPlus(nn.Module):
 class GenerateSparseMask(CachesWeights, nn.Module):
     """submodule.py:347-372: squared difference between the level's features and the upsampled
     previous level's, reduced to one logit per pixel."""
-    _CACHE_ATTRS = ("_hp", "_hp_key", "_hp_src")
+    _CACHE_ATTRS = cache_attrs("_hp")
 
     def __init__(self, in_channels, down_scale):
         super().__init__()
@@ -587,48 +434,27 @@ class GenerateSparseMask(CachesWeights, nn.Module):
         return self.conv(d * d).squeeze(1)
 
     def _host_params(self):
-        """The 3x3 and 1x1 units of ``conv`` with BatchNorm folded, as host arrays (90 floats; one device ->
+        """The 3x3 and 1x1 units of ``conv`` with BatchNorm folded, as host arrays (92 floats; one device ->
         host copy per weight version; stage0.source_key: a write through ``.data`` after the first forward needs
         ``drop_weight_caches``)."""
-        import ctypes
         u3, u1 = self.conv[0], self.conv[1]
         ts = [t for u in (u3, u1) for t in (u.conv.weight, u.bn.weight, u.bn.bias, u.bn.running_mean, u.bn.running_var)]
-        key = source_key(ts, u3.bn.eps, u1.bn.eps)
-        if getattr(self, "_hp_key", None) != key:
-            with torch.no_grad():
-                def fold(u):
-                    sc = u.bn.weight.float() / torch.sqrt(u.bn.running_var.float() + u.bn.eps)
-                    return sc, u.bn.bias.float() - u.bn.running_mean.float() * sc
-                s3, b3 = fold(u3)
-                s1, b1 = fold(u1)
-                flat = torch.cat([u3.conv.weight.float().reshape(-1), s3, b3, u1.conv.weight.float().reshape(-1),
-                                  s1, b1]).cpu().tolist()
-            arr = lambda v: (ctypes.c_float * len(v))(*v)
-            self._hp = (arr(flat[0:81]), arr(flat[81:84]), arr(flat[84:87]), arr(flat[87:90]), flat[90], flat[91])
-            self._hp_key, self._hp_src = key, source_hold(ts)
-        return self._hp
+
+        def build():
+            flat = [v for u in (u3, u1) for v in (u.conv.weight.float().reshape(-1),) + fold_bn(u.bn)]
+            return ops2d.detail_mask_params(torch.cat(flat).cpu().tolist())
+        return self._cached("_hp", ts, (u3.bn.eps, u1.bn.eps), build)
 
     def mask(self, cur, pre, thold, want_bits=False):
         """``(sigmoid(self(cur, pre)) > thold)`` as a float 0/1 plane [B,H,W] (SparseDenseNetRefinementMask.py:
         148-170).  On the GPU in eval mode the squared difference, both convolutions of ``conv``, the sigmoid
-        and the threshold are one kernel (csrc/maskgen.hip)."""
-        if (self.training or not cur.is_cuda or cur.dtype != torch.float32 or torch.is_grad_enabled() or
-                os.environ.get("DECNET_CONV2D", "hip") != "hip" or cur.shape[-2] > 65535):
+        and the threshold are one kernel (csrc/maskgen.hip).  want_bits: also the bit-packed copy the SpaMat kernels
+        read."""
+        if not hip_gate(cur, self.training) or cur.shape[-2] > 65535:
             m = (torch.sigmoid(self(cur, pre)) > thold).to(cur.dtype)
             return (m, None) if want_bits else m
-        from . import _lib
-        from .ops import _stream
-        a, b = self.conv_sub(cur).contiguous(), self.deconv(pre).contiguous()
-        B, _, H, W = a.shape
-        w3, s3, b3, w1, s1, b1 = self._host_params()
-        out = torch.empty((B, H, W), dtype=torch.float32, device=a.device)
-        # want_bits: also the bit-packed copy the SpaMat kernels read (64 pixels per int64 word)
-        bits = torch.empty((B, H, (W + 63) // 64), dtype=torch.int64, device=a.device) if want_bits else None
-        with torch.cuda.device(a.device):
-            _lib.check(_lib.lib().decnet_detail_mask(a.data_ptr(), b.data_ptr(), w3, s3, b3, w1, s1, b1, float(thold),
-                                                     out.data_ptr(), None, bits.data_ptr() if want_bits else None,
-                                                     B, H, W, _stream(a)),
-                       "decnet_detail_mask")
+        out, bits = ops2d.detail_mask(self.conv_sub(cur).contiguous(), self.deconv(pre).contiguous(), self._host_params(),
+                                      thold, want_bits)
         return (out, bits) if want_bits else out
 
 
@@ -647,30 +473,14 @@ class DynamicUpsampling(nn.Module):
     def forward(self, disp, fea):
         B, h, w = disp.shape
         s2 = self.s ** 2
-        hip = (self.s == 3 and fea.is_cuda and fea.dtype == torch.float32 and not torch.is_grad_enabled() and
-               h <= 65535 and B * (fea.shape[1] + 1) <= 65535 and os.environ.get("DECNET_CONV2D", "hip") == "hip" and
-               tuple(fea.shape[-2:]) == (3 * h, 3 * w))
-        if hip:                                         # cat(disp, unfold(fea)) as one pass (csrc/unfold.hip)
-            from . import _lib
-            from .ops import _stream
-            f, dp = fea.contiguous(), disp.contiguous()
-            wts = torch.empty((B, 9 * f.shape[1] + 1, h, w), dtype=torch.float32, device=f.device)
-            with torch.cuda.device(f.device):
-                _lib.check(_lib.lib().decnet_unfold3_cat(f.data_ptr(), dp.data_ptr(), wts.data_ptr(), B, f.shape[1], h, w,
-                                                         _stream(f)), "decnet_unfold3_cat")
+        if (self.s == 3 and hip_gate(fea) and h <= 65535 and B * (fea.shape[1] + 1) <= 65535 and
+                tuple(fea.shape[-2:]) == (3 * h, 3 * w)):       # cat(disp, unfold(fea)) as one pass (csrc/unfold.hip)
+            wts = ops2d.unfold3_cat(fea.contiguous(), disp.contiguous())
         else:
             wts = torch.cat((disp.unsqueeze(1), F.unfold(fea, self.s, stride=self.s).view(B, -1, h, w)), 1)
         logits = self.weight_learning(wts)
-        if (self.s == 3 and logits.is_cuda and logits.dtype == torch.float32 and not torch.is_grad_enabled() and
-                h <= 65535 and os.environ.get("DECNET_CONV2D", "hip") == "hip"):
-            from . import _lib
-            from .ops import _stream
-            lg, dp = logits.contiguous(), disp.contiguous()
-            out = torch.empty((B, 3 * h, 3 * w), dtype=torch.float32, device=lg.device)
-            with torch.cuda.device(lg.device):
-                _lib.check(_lib.lib().decnet_dynamic_upsample3(lg.data_ptr(), dp.data_ptr(), out.data_ptr(), B, h, w,
-                                                               _stream(lg)), "decnet_dynamic_upsample3")
-            return out
+        if self.s == 3 and hip_gate(logits) and h <= 65535:
+            return ops2d.dynamic_upsample3(logits.contiguous(), disp.contiguous())
         wts = F.softmax(logits.view(B, s2, 9, h * w), 2)
         nb = F.unfold(self.pad(disp.unsqueeze(1)), 3).unsqueeze(1)
         up = (nb * wts).sum(2).view(B, s2, h, w)
@@ -714,16 +524,8 @@ def warp_by_disparity(right, disp):
     """Refinement.get_warped_feats_by_homgrp (submodule.py:719-745): the same stretched,
     half-pixel-shifted bilinear warp as stage 0, one disparity per pixel."""
     B, C, H, W = right.shape
-    if (right.is_cuda and right.dtype == torch.float32 and not torch.is_grad_enabled() and H > 1 and W > 1 and
-            H <= 65535 and os.environ.get("DECNET_CONV2D", "hip") == "hip"):
-        from . import _lib
-        from .ops import _stream
-        r, d = right.contiguous(), disp.contiguous()
-        out = torch.empty_like(r)
-        with torch.cuda.device(r.device):
-            _lib.check(_lib.lib().decnet_warp_disparity(r.data_ptr(), d.data_ptr(), out.data_ptr(), B, C, H, W,
-                                                        _stream(r)), "decnet_warp_disparity")
-        return out
+    if hip_gate(right) and H > 1 and W > 1 and H <= 65535:
+        return ops2d.warp_disparity(right.contiguous(), disp.contiguous())
     ys, xs = torch.meshgrid(torch.arange(H, dtype=right.dtype, device=right.device),
                             torch.arange(W, dtype=right.dtype, device=right.device), indexing="ij")
     cx = (xs.unsqueeze(0) - disp) / ((W - 1.0) / 2.0) - 1.0
@@ -849,7 +651,7 @@ class SparseDenseNetRefinementMask(nn.Module):
             lmask, rmask, lbits, rbits = masks
             D = max_disp_of(stage)
             res = None
-            if lbits is not None and rbits is not None and os.environ.get("DECNET_SPAMAT_BITS", "1") == "1":
+            if lbits is not None and rbits is not None and spamat_bits_switch():
                 try:
                     res = spamatvar_forward_bits(L.contiguous(), R.contiguous(), lbits, rbits, D, out=out)
                 except DecnetHipError as e:             # shapes only the float-mask entry's fallback kernels cover

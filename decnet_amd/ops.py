@@ -13,11 +13,12 @@ _F32 = torch.float32
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 
+# the current HIP stream of device `index` as a raw handle (what the C ABI takes as void*)
+_stream_of = _raw_stream or (lambda index: torch.cuda.current_stream(index).cuda_stream)
+
+
 def _stream(t):
-    """The current HIP stream of t's device as a raw handle (what the C ABI takes as void*)."""
-    if _raw_stream is not None:
-        return _raw_stream(t.device.index)
-    return torch.cuda.current_stream(t.device).cuda_stream
+    return _stream_of(t.device.index)
 
 
 def _chk(name, t, shape=None):
@@ -39,25 +40,6 @@ def _chk(name, t, shape=None):
     raise ValueError("%s has shape %s, expected %s" % (name, tuple(t.shape), tuple(shape)))
 
 
-class _on_device:
-    """`with _on_device(t):` = torch.cuda.device(t.device), free when that device is already current (the
-    reference wraps its launches in torch.cuda.device_of, functions/SpaMat.py:24)."""
-    __slots__ = ("idx", "ctx")
-
-    def __init__(self, t):
-        self.idx = t.device.index
-        self.ctx = None
-
-    def __enter__(self):
-        if self.idx != torch.cuda.current_device():
-            self.ctx = torch.cuda.device(self.idx)
-            self.ctx.__enter__()
-
-    def __exit__(self, *exc):
-        if self.ctx is not None:
-            self.ctx.__exit__(*exc)
-
-
 _FN = {}
 
 
@@ -67,6 +49,22 @@ def _fn(name):
     if f is None:
         f = _FN[name] = getattr(_lib.lib(), name)
     return f
+
+
+def _call(name, like, *args, returns_rc=False):
+    """THE way to make a C call: entry `name` on like's device (as torch.cuda.device_of, functions/SpaMat.py:24), the
+    current stream of that device appended as the last argument, the result checked under the entry's own name.  returns_rc: DECNET_ERR_UNSUPPORTED is an answer, not an
+    error, and is returned (0 otherwise) -- for the entries whose caller has another route."""
+    fn = _FN.get(name) or _fn(name)
+    idx = like.device.index
+    if idx == torch.cuda.current_device():          # (this runs for every launch: no context object on the usual path)
+        rc = fn(*args, _stream_of(idx))
+    else:
+        with torch.cuda.device(idx):
+            rc = fn(*args, _stream_of(idx))
+    if rc and not (returns_rc and rc == _lib.UNSUPPORTED):
+        _lib.check(rc, name)
+    return rc
 
 
 def _same_device(*ts):
@@ -113,24 +111,20 @@ def workspace_floats(B, C, H, W, D, which):
     return n
 
 
-def _call(name, which, like, dims, *ptrs):
-    """Entry `name` on like's device and current stream: the original entry where one band takes the call, else its
-    `_ws` twin on a workspace allocated here."""
+def _call_banded(name, which, like, dims, *ptrs):
+    """Entry `name` where one band takes the call, else its `_ws` twin on a workspace allocated here."""
     n = workspace_floats(*dims, which)
-    with _on_device(like):
-        if n == 0:
-            rc = _fn(name)(*ptrs, *dims, _stream(like))
-        else:
-            ws = torch.empty(n, dtype=_F32, device=like.device)        # torch allocations are 16-byte aligned
-            rc = _fn(name + "_ws")(*ptrs, *dims, ws.data_ptr(), n, _stream(like))
-    _lib.check(rc, name if n == 0 else name + "_ws")
+    if n == 0:
+        return _call(name, like, *ptrs, *dims)
+    ws = torch.empty(n, dtype=_F32, device=like.device)                # torch allocations are 16-byte aligned
+    _call(name + "_ws", like, *ptrs, *dims, ws.data_ptr(), n)
 
 
 def spamat_forward(ref, tar, rmask, tmask, output, sum_sim, max_cost, max_disp):
     B, C, H, W, D = _feat_args(ref, tar, rmask, tmask, max_disp)
     for n, t in (("output", output), ("sum_similarities", sum_sim), ("max_cost", max_cost)):
         _chk(n, t, (B, H, W))
-    _call("decnet_spamat_forward", WS_SPAMAT_FWD, ref, (B, C, H, W, D),
+    _call_banded("decnet_spamat_forward", WS_SPAMAT_FWD, ref, (B, C, H, W, D),
           ref.data_ptr(), tar.data_ptr(), rmask.data_ptr(), tmask.data_ptr(), output.data_ptr(),
           sum_sim.data_ptr(), max_cost.data_ptr())
 
@@ -143,7 +137,7 @@ def spamat_backward(ref, tar, rmask, tmask, output, sum_sim, max_cost, grad_out,
         _chk(n, t, (B, H, W))
     _chk("grad_ref_feas", grad_ref, (B, C, H, W))
     _chk("grad_tar_feas", grad_tar, (B, C, H, W))
-    _call("decnet_spamat_backward", WS_SPAMAT_BWD, ref, (B, C, H, W, D),
+    _call_banded("decnet_spamat_backward", WS_SPAMAT_BWD, ref, (B, C, H, W, D),
           ref.data_ptr(), tar.data_ptr(), rmask.data_ptr(), tmask.data_ptr(), output.data_ptr(),
           sum_sim.data_ptr(), max_cost.data_ptr(), grad_out.data_ptr(), grad_ref.data_ptr(),
           grad_tar.data_ptr())
@@ -154,7 +148,7 @@ def spavar_forward(ref, tar, rmask, tmask, disparity, output, sum_sim, max_cost,
     for n, t in (("disparity", disparity), ("output", output), ("sum_similarities", sum_sim),
                  ("max_cost", max_cost)):
         _chk(n, t, (B, H, W))
-    _call("decnet_spavar_forward", WS_SPAVAR_FWD, ref, (B, C, H, W, D),
+    _call_banded("decnet_spavar_forward", WS_SPAVAR_FWD, ref, (B, C, H, W, D),
           ref.data_ptr(), tar.data_ptr(), rmask.data_ptr(), tmask.data_ptr(),
           disparity.data_ptr(), output.data_ptr(), sum_sim.data_ptr(), max_cost.data_ptr())
 
@@ -167,7 +161,7 @@ def spavar_backward(ref, tar, rmask, tmask, disparity, output, sum_sim, max_cost
         _chk(n, t, (B, H, W))
     _chk("grad_ref_feas", grad_ref, (B, C, H, W))
     _chk("grad_tar_feas", grad_tar, (B, C, H, W))
-    _call("decnet_spavar_backward", WS_SPAVAR_BWD, ref, (B, C, H, W, D),
+    _call_banded("decnet_spavar_backward", WS_SPAVAR_BWD, ref, (B, C, H, W, D),
           ref.data_ptr(), tar.data_ptr(), rmask.data_ptr(), tmask.data_ptr(),
           disparity.data_ptr(), output.data_ptr(), sum_sim.data_ptr(), max_cost.data_ptr(),
           grad_out.data_ptr(), grad_ref.data_ptr(), grad_tar.data_ptr(), grad_disp.data_ptr())
@@ -194,7 +188,7 @@ def spamatvar_forward_bits(ref, tar, rbits, tbits, max_disp, out=None):
     o, v, s, m = out
     for n, t in (("output", o), ("variance", v), ("sum_similarities", s), ("max_cost", m)):
         _chk(n, t, (B, H, W))
-    _call("decnet_spamatvar_forward_bits", WS_FUSED_BITS_FWD, ref, (B, C, H, W, D),
+    _call_banded("decnet_spamatvar_forward_bits", WS_FUSED_BITS_FWD, ref, (B, C, H, W, D),
           ref.data_ptr(), tar.data_ptr(), rbits.data_ptr(), tbits.data_ptr(), o.data_ptr(),
           v.data_ptr(), s.data_ptr(), m.data_ptr())
     return o, v, s, m
@@ -210,7 +204,7 @@ def spamatvar_forward(ref, tar, rmask, tmask, max_disp, out=None):
     o, v, s, m = out
     for n, t in (("output", o), ("variance", v), ("sum_similarities", s), ("max_cost", m)):
         _chk(n, t, (B, H, W))
-    _call("decnet_spamatvar_forward", WS_FUSED_FWD, ref, (B, C, H, W, D),
+    _call_banded("decnet_spamatvar_forward", WS_FUSED_FWD, ref, (B, C, H, W, D),
           ref.data_ptr(), tar.data_ptr(), rmask.data_ptr(), tmask.data_ptr(), o.data_ptr(),
           v.data_ptr(), s.data_ptr(), m.data_ptr())
     return o, v, s, m
@@ -260,11 +254,8 @@ def stage_loss_forward(pred, dense, sparse, fusion, soft_mask, left_mask, gt, gt
     _chk64("row_sums", row_sums, (B * H, 8))
     _chk64("sums", sums, (8,))
     _chk("terms", terms, (5,))
-    with _on_device(pred):
-        rc = _fn("decnet_stage_loss_forward")(pred.data_ptr(), *opt, gt.data_ptr(), float(gt_max), float(down_size),
-                                              int(skip_rows), row_sums.data_ptr(), sums.data_ptr(), terms.data_ptr(),
-                                              B, H, W, _stream(pred))
-    _lib.check(rc, "decnet_stage_loss_forward")
+    _call("decnet_stage_loss_forward", pred, pred.data_ptr(), *opt, gt.data_ptr(), float(gt_max), float(down_size),
+          int(skip_rows), row_sums.data_ptr(), sums.data_ptr(), terms.data_ptr(), B, H, W)
     return terms
 
 
@@ -278,8 +269,5 @@ def stage_loss_backward(pred, dense, sparse, fusion, soft_mask, left_mask, gt, g
     for n, t in (("g_pred", g_pred), ("g_dense", g_dense), ("g_sparse", g_sparse), ("g_fusion", g_fusion),
                  ("g_soft", g_soft)):
         outs.append(0 if t is None else _chk(n, t, (B, H, W)).data_ptr())
-    with _on_device(pred):
-        rc = _fn("decnet_stage_loss_backward")(pred.data_ptr(), *opt, gt.data_ptr(), float(gt_max), float(down_size),
-                                               int(skip_rows), sums.data_ptr(), grad_terms.data_ptr(), *outs,
-                                               B, H, W, _stream(pred))
-    _lib.check(rc, "decnet_stage_loss_backward")
+    _call("decnet_stage_loss_backward", pred, pred.data_ptr(), *opt, gt.data_ptr(), float(gt_max), float(down_size),
+          int(skip_rows), sums.data_ptr(), grad_terms.data_ptr(), *outs, B, H, W)

@@ -1,0 +1,290 @@
+"""Tensor-level wrappers of the 2-D trunk and stage-0 entries of the C ABI (include/decnet_hip.h): one function per
+entry that model.py and stage0.py call.  Like ops.py for SpaMat / SpaVar: a wrapper takes tensors, checks them with
+``ops._chk`` (on the GPU, fp32, contiguous, the shapes that follow from the others -- the C side takes raw pointers), goes
+through ``ops._call`` (device, current stream, checked return code) and allocates its output unless ``out`` is given.
+Every check comes before the first library lookup.  ``.contiguous()`` is the caller's business.
+"""
+import ctypes
+from functools import partial
+
+import torch
+
+from . import _lib
+from .ops import _F32, _call, _chk, _fn
+
+_U8 = torch.uint8
+
+
+def _run(name, ins, out, shape, *ints):
+    """Entry `name`(inputs..., y, ints...) with y = out, or a new fp32 tensor of `shape` beside the first input; -> y."""
+    y = torch.empty(shape, dtype=_F32, device=ins[0].device) if out is None else _chk("out", out, shape)
+    _call(name, y, *[t.data_ptr() for t in ins], y.data_ptr(), *ints)
+    return y
+
+
+def _flat(name, t, n):
+    """A buffer of at least n floats (workspaces grow only, so they may be longer) -> its address."""
+    if _chk(name, t).numel() < n:
+        raise ValueError("%s holds %d floats, the call needs %d" % (name, t.numel(), n))
+    return t.data_ptr()
+
+
+def _opt(name, t, shape=None):
+    return None if t is None else _chk(name, t, shape).data_ptr()
+
+
+def _wss(w, scale, shift, wtype=_F32):
+    """Packed weight (a flat library-format buffer), folded scale and shift [Cout] -> (w, scale, shift), Cout."""
+    if not (w.is_cuda and w.dtype is wtype and w.is_contiguous()):
+        raise TypeError("the packed weight must be a contiguous %s tensor on the GPU" % wtype)
+    _chk("shift", shift, _chk("scale", scale).shape)
+    return (w, scale, shift), scale.shape[0]
+
+
+def size(query, *dims):
+    """A size query of the library (decnet_`query`: a pure host function of its arguments)."""
+    return _fn("decnet_" + query)(*dims)
+
+
+# ---- the few-channel fp32 kernels (csrc/conv2d_small.hip) and the bf16x3 matrix-core kernels (csrc/conv2d_mfma.hip) ---------
+def conv2d_pack_weight(w, transposed):
+    """Conv2d [Cout,Cin,k,k] / ConvTranspose2d [Cin,Cout,k,k] weight -> the few-channel kernels' layout."""
+    ci, co = _chk("weight", w).shape[:2] if transposed else (w.shape[1], w.shape[0])
+    dims = (ci, co, w.shape[2], int(transposed))
+    return _run("decnet_conv2d_pack_weight", (w,), None, (size("conv2d_packed_floats", *dims),), *dims)
+
+
+def conv2d_mfma_pack_weight(w, cin, k):
+    """[Cout, cin k k] fp32 -> bf16 terms in the operand layout (a stride-3 [Cout,Ci,3,3] goes in as cin = 9 Ci, k = 1)."""
+    wp = torch.empty(size("conv2d_mfma_packed_bytes", cin, _chk("weight", w).shape[0], k), dtype=_U8, device=w.device)
+    _call("decnet_conv2d_mfma_pack_weight", w, w.data_ptr(), wp.data_ptr(), cin, w.shape[0], k)
+    return wp
+
+
+def deconv2d_mfma_pack_weight(w):
+    ci, co = _chk("weight", w).shape[:2]
+    wp = torch.empty(size("deconv2d_mfma_packed_bytes", ci, co), dtype=_U8, device=w.device)
+    _call("decnet_deconv2d_mfma_pack_weight", w, w.data_ptr(), wp.data_ptr(), ci, co)
+    return wp
+
+
+def _conv2d(name, up, wtype, x, w, scale, shift, cin, *ints, out=None):
+    """A single-input entry: x [B,cin,H,W] -> [B,Cout,H,W] (up None), [B,Cout,3H,3W] (True), [B,Cout,ceil(H/3),ceil(W/3)]
+    (False); ints: (k, dil, relu) or (relu)."""
+    B, C, H, W = _chk("x", x).shape
+    if C != cin:
+        raise ValueError("the input has %d channels, the layer takes %d" % (C, cin))
+    wss, Co = _wss(w, scale, shift, wtype)
+    hw = (H, W) if up is None else (3 * H, 3 * W) if up else ((H - 1) // 3 + 1, (W - 1) // 3 + 1)
+    return _run(name, (x,) + wss, out, (B, Co) + hw, B, cin, Co, H, W, *ints)
+
+
+def _conv2d_cat(name, wtype, xs, w, scale, shift, cin, k, dil, relu, out=None, epi=None, ea=None, eb=None):
+    """A `cat` entry: the parts xs [B,c_i,H,W] of a channel concatenation that is never materialised -> [B,Cout,H,W]."""
+    B, _, H, W = _chk("input part", xs[0]).shape
+    for t in xs[1:]:
+        _chk("input part", t, (B, t.shape[1], H, W))
+    cins, n = [int(t.shape[1]) for t in xs], len(xs)
+    if sum(cins) != cin:
+        raise ValueError("the parts have %d channels together, the layer takes %d" % (sum(cins), cin))
+    wss, Co = _wss(w, scale, shift, wtype)
+    y = torch.empty((B, Co, H, W), dtype=_F32, device=xs[0].device) if out is None else _chk("out", out, (B, Co, H, W))
+    args = ((ctypes.c_void_p * n)(*[t.data_ptr() for t in xs]), (ctypes.c_int * n)(*cins), n, *[t.data_ptr() for t in wss],
+            y.data_ptr(), B)
+    if epi is None:
+        _call(name, y, *args, Co, H, W, k, dil, relu)
+    elif Co != 1:
+        raise ValueError("the fused tail is a single-output layer's, this one has %d outputs" % Co)
+    else:
+        _call(name, y, *args, H, W, k, dil, relu, int(epi), _chk("ea", ea, (B, H, W)).data_ptr(), _opt("eb", eb, (B, H, W)))
+    return y
+
+
+# (x, w, scale, shift, cin, k, dil, relu, out=None) / (x, w, scale, shift, cin, relu, out=None); relu: 0 or 1
+conv2d_bn_act = partial(_conv2d, "decnet_conv2d_bn_act", None, _F32)
+conv2d_k3s3_bn_act = partial(_conv2d, "decnet_conv2d_k3s3_bn_act", False, _F32)
+deconv2d_k3s3_bn_act = partial(_conv2d, "decnet_deconv2d_k3s3_bn_act", True, _F32)
+deconv2d_mfma_k3s3_bn_act = partial(_conv2d, "decnet_deconv2d_mfma_k3s3_bn_act", True, _U8)
+# (xs, w, scale, shift, cin, k, dil, relu, out=None)
+conv2d_cat_bn_act = partial(_conv2d_cat, "decnet_conv2d_cat_bn_act", _F32)
+conv2d_mfma_cat_bn_act = partial(_conv2d_cat, "decnet_conv2d_mfma_cat_bn_act", _U8)
+
+
+def conv2d_cat_epilogue(xs, w, scale, shift, cin, k, dil, relu, epi, ea, eb=None, out=None):
+    """The single-output layer with its fused tail: epi 1 = ea * (1 - sigmoid(v)) + sigmoid(v) * eb, 2 = ea + v."""
+    return _conv2d_cat("decnet_conv2d_cat_epilogue", _F32, xs, w, scale, shift, cin, k, dil, relu, out, int(epi), ea, eb)
+
+
+def bias_act_inplace(x, b, relu):
+    B, Co, H, W = _chk("x", x).shape
+    _call("decnet_bias_act_inplace", x, x.data_ptr(), _chk("bias", b, (Co,)).data_ptr(), B, Co, H, W, relu)
+    return x
+
+
+def s2d3_pad1(x, out=None):
+    """Space to depth of a k 3, stride 3, padding 1 convolution: [B,C,H,W] -> [B,9C,ceil(H/3),ceil(W/3)]."""
+    B, C, H, W = _chk("x", x).shape
+    return _run("decnet_s2d3_pad1", (x,), out, (B, 9 * C, (H - 1) // 3 + 1, (W - 1) // 3 + 1), B, C, H, W)
+
+
+# ---- the ASPP block as a per-tap GEMM (csrc/tapconv.hip) -------------------------------------------------------------
+def tapconv_pack_weight(w, u, tap0):
+    co, ci, k, _ = _chk("weight", w).shape
+    _call("decnet_tapconv_pack_weight", w, w.data_ptr(), _chk("u", u).data_ptr(), co, ci, k, tap0)
+
+
+def tapconv_split_weight(u, ci, ntaps):
+    _call("decnet_tapconv_split_weight", u, _flat("u", u, size("tapconv_weight_floats", ci, ntaps)), ci, ntaps)
+
+
+def tapconv_to_chunks(x):
+    B, Ci, H, W = _chk("x", x).shape
+    return _run("decnet_tapconv_to_chunks", (x,), None, (size("tapconv_chunk_floats", B, Ci, H, W),), B, Ci, H, W)
+
+
+def tap_gemm(V, u, P, Ci, Co, ntaps, split):
+    _chk("u", u)
+    return _run("decnet_tap_gemm", (_chk("V", V), u), None, (ntaps * ((Co + 15) // 16) * 16 * P,), P, Ci, Co, ntaps, split)
+
+
+def tapconv_gather(T, scale, shift, B, Co, H, W, tap0, ks, dil, relu, out=None):
+    nb, ints = len(ks), lambda v: (ctypes.c_int * len(v))(*v)
+    _chk("shift", shift, _chk("scale", scale, (nb * Co,)).shape)
+    _flat("T", T, sum(k * k for k in ks) * ((Co + 15) // 16) * 16 * B * H * W)
+    return _run("decnet_tapconv_gather", (T, scale, shift), out, (B, nb * Co, H, W), B, Co, H, W, nb, ints(tap0), ints(ks),
+                ints(dil), relu)
+
+
+# ---- the element-wise passes of the trunk ----------------------------------------------------------------------------
+def unfold3_cat(fea, disp, out=None):
+    """cat(disp, unfold(fea, 3, stride 3)): fea [B,C,3h,3w], disp [B,h,w] -> [B,9C+1,h,w]."""
+    B, h, w = _chk("disp", disp).shape
+    C = _chk("fea", fea).shape[1]
+    _chk("fea", fea, (B, C, 3 * h, 3 * w))
+    return _run("decnet_unfold3_cat", (fea, disp), out, (B, 9 * C + 1, h, w), B, C, h, w)
+
+
+def dynamic_upsample3(logits, disp, out=None):
+    B, h, w = _chk("disp", disp).shape
+    _chk("logits", logits, (B, 81, h, w))
+    return _run("decnet_dynamic_upsample3", (logits, disp), out, (B, 3 * h, 3 * w), B, h, w)
+
+
+def warp_disparity(right, disp, out=None):
+    B, C, H, W = _chk("right", right).shape
+    _chk("disp", disp, (B, H, W))
+    return _run("decnet_warp_disparity", (right, disp), out, (B, C, H, W), B, C, H, W)
+
+
+def detail_mask_params(flat):
+    """The 92 folded host values of GenerateSparseMask.conv as the entry takes them: w3x3, scale3, shift3, w1x1, s1, b1."""
+    arr = lambda v: (ctypes.c_float * len(v))(*v)  # noqa: E731
+    return arr(flat[0:81]), arr(flat[81:84]), arr(flat[84:87]), arr(flat[87:90]), flat[90], flat[91]
+
+
+def detail_mask(cur3, pre3, params, thold, want_bits=False, out=None):
+    """-> (mask [B,H,W] float 0/1, bits: None or the bit-packed copy the SpaMat kernels read, 64 pixels per int64 word)."""
+    B, C, H, W = _chk("cur3", cur3).shape
+    _chk("pre3", pre3, (B, 3, H, W))
+    if C != 3:
+        raise ValueError("cur3 has %d channels, the layer takes 3" % C)
+    y = torch.empty((B, H, W), dtype=_F32, device=cur3.device) if out is None else _chk("out", out, (B, H, W))
+    bits = torch.empty((B, H, (W + 63) // 64), dtype=torch.int64, device=cur3.device) if want_bits else None
+    _call("decnet_detail_mask", cur3, cur3.data_ptr(), pre3.data_ptr(), *params, float(thold), y.data_ptr(), None,
+          bits.data_ptr() if want_bits else None, B, H, W)
+    return y, bits
+
+
+# ---- stage 0 (channels-last [B,D,H,W,C] volumes; the activation buffers are flat, grow-only workspaces) ------------------
+def ncdhw_to_ndhwc(x, out=None):
+    B, C, D, H, W = _chk("x", x).shape
+    return _run("decnet_ncdhw_to_ndhwc", (x,), out, (B, D, H, W, C), B, C, D, H, W)
+
+
+def costvol_forward_cf(left, right, D, cost_func, out=None):
+    """[B,C,H,W] x2 -> channels-last cost volume [B,D,H,W,C] ([B,D,H,W,2C] for cost_func "cat")."""
+    B, C, H, W = _chk("left_feature_map", left).shape
+    _chk("right_feature_map", right, (B, C, H, W))
+    return _run("decnet_costvol_forward_cf", (left, right), out, (B, D, H, W, 2 * C if cost_func == "cat" else C),
+                B, C, H, W, D, _lib.COST_FUNC[cost_func])
+
+
+def conv3d_pointwise(x, w, out=None):
+    """Conv3d k 1 without bias on a channels-last volume: x [B,D,H,W,Ci], w [Co,Ci] -> [B,D,H,W,Co]."""
+    B, D, H, W, Ci = _chk("x", x).shape
+    Co = _chk("w", w).shape[0]
+    _chk("w", w, (Co, Ci))
+    return _run("decnet_conv3d_pointwise", (x, w), out, (B, D, H, W, Co), B, Ci, Co, D * H * W, Ci, 1)
+
+
+def conv3d_pack_weight(w):
+    """[Co,Ci,3,3,3] -> [27,Ci,CoP]."""
+    Co, Ci = _chk("weight", w).shape[:2]
+    CoP = size("conv3d_packed_cout", Co)
+    if CoP < 0:
+        raise _lib.DecnetHipError("Conv3d with %d output channels is not supported (<= 224)" % Co)
+    return _run("decnet_conv3d_pack_weight", (w,), None, (27, Ci, CoP), Co, Ci)
+
+
+def conv3d_wino_pack_weight(w, variant):
+    Co, Ci = _chk("weight", w).shape[:2]
+    n = size("conv3d_wino_weight_floats", Ci, variant)
+    return _run("decnet_conv3d_wino_pack_weight", (w,), None, (n,), Co, Ci, variant)
+
+
+def conv3d_bn_act(src, w, scale, shift, res, dst, dims, Ci, Co, relu, ws=None, variant=None):
+    """One Conv3dUnit on flat buffers, dims = (B, D, H, W): dst = act(bn(conv(src))) (+ res).  decnet_conv3d_bn_act (27-tap
+    implicit GEMM, w from conv3d_pack_weight), or with ws (size conv3d_wino_workspace_floats) decnet_conv3d_wino_bn_act
+    (Winograd `variant`, w from conv3d_wino_pack_weight)."""
+    n = dims[0] * dims[1] * dims[2] * dims[3]
+    _chk("shift", shift, _chk("scale", scale, (Co,)).shape)
+    p = (_flat("src", src, n * Ci), _chk("weight", w).data_ptr(), scale.data_ptr(), shift.data_ptr(),
+         None if res is None else _flat("res", res, n * Co), _flat("dst", dst, n * Co))
+    if ws is None:
+        _call("decnet_conv3d_bn_act", src, *p, *dims, Ci, Co, relu)
+    else:
+        _call("decnet_conv3d_wino_bn_act", src, *p, _chk("ws", ws).data_ptr(), *dims, Ci, Co, relu, variant)
+
+
+def conv3d_wino_stack_bn_act(x, layers, res_src, res_dst, out, ws, dims, C, variant):
+    """The C -> C units `layers` (dicts of u, scale, shift) as ONE fused stack; False: "unsupported", nothing launched."""
+    n = dims[0] * dims[1] * dims[2] * dims[3] * C
+    for p in layers:
+        _chk("u", p["u"])
+        _chk("shift", p["shift"], _chk("scale", p["scale"], (C,)).shape)
+    u, sc, sh = ((ctypes.c_void_p * len(layers))(*[p[k].data_ptr() for p in layers]) for k in ("u", "scale", "shift"))
+    return 0 == _call("decnet_conv3d_wino_stack_bn_act", x, _flat("x", x, n), u, sc, sh, len(layers), res_src, res_dst,
+                      _flat("out", out, n), _chk("ws", ws).data_ptr(), *dims, C, variant, returns_rc=True)
+
+
+def conv3d_cout1_softargmax(x, w, scale, shift, dims, Ci, reg=None, pred=None, ws=None):
+    """The last unit (one output channel; scale, shift: host floats) + softmax over D + expectation: x -> (reg [B,D,H,W]
+    if given, pred [B,H,W]).  ws (size conv3d_cout1_workspace_floats): the tap-GEMM form, decnet_conv3d_cout1_softargmax_ws."""
+    B, D, H, W = dims
+    _chk("weight", w, (1, Ci, 3, 3, 3))
+    y = torch.empty((B, H, W), dtype=_F32, device=x.device) if pred is None else _chk("pred", pred, (B, H, W))
+    p = (_flat("x", x, B * D * H * W * Ci), w.data_ptr(), scale, shift, _opt("reg", reg, dims), y.data_ptr())
+    if ws is None:
+        _call("decnet_conv3d_cout1_softargmax", x, *p, *dims, Ci)
+    else:
+        _call("decnet_conv3d_cout1_softargmax_ws", x, *p, _chk("ws", ws).data_ptr(), *dims, Ci)
+    return y
+
+
+def stage0_forward_cf(left, right, params, w_pre, ws, D, variant, cost_func, reg=None, pred=None):
+    """The whole stage-0 branch in one entry: [B,C,H,W] x2 -> pred [B,H,W] (and reg [B,D,H,W] where given); params: a
+    _lib.Stage0Params, ws: size stage0_cf_workspace_floats."""
+    B, C, H, W = _chk("left_feature_map", left).shape
+    _chk("right_feature_map", right, (B, C, H, W))
+    y = torch.empty((B, H, W), dtype=_F32, device=left.device) if pred is None else _chk("pred", pred, (B, H, W))
+    _call("decnet_stage0_forward_cf", left, left.data_ptr(), right.data_ptr(), ctypes.byref(params), _opt("w_pre", w_pre),
+          _chk("ws", ws).data_ptr(), _opt("reg", reg, (B, D, H, W)), y.data_ptr(), B, C, H, W, D, variant,
+          _lib.COST_FUNC[cost_func])
+    return y
+
+
+def disparity_regression(cost_vol, disp_samples, out=None):
+    """softmax over dim 1, expectation of disp_samples: [B,S,H,W] x2 -> [B,H,W]."""
+    B, S, H, W = _chk("cost_vol", cost_vol).shape
+    _chk("disp_samples", disp_samples, (B, S, H, W))
+    return _run("decnet_disparity_regression", (cost_vol, disp_samples), out, (B, H, W), B, S, H, W)

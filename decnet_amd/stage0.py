@@ -18,8 +18,8 @@ import os
 import torch
 import torch.nn as nn
 
-from . import _lib
-from .ops import _chk, _stream
+from . import _lib, ops2d
+from .ops import _chk
 
 BN_EPS = 1e-5
 
@@ -42,6 +42,25 @@ def source_hold(ts):
     return [t.detach() for t in ts]
 
 
+def fold_bn(bn, fp32=True):
+    """Eval-mode BatchNorm as a per-channel (scale, shift): y = scale * x + shift.  fp32=False folds in the parameters'
+    own dtype (Unit._folded_torch, whose product goes back into a convolution of that dtype)."""
+    w, b, mean, var = ((t.float() if fp32 else t) for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var))
+    scale = w / torch.sqrt(var + bn.eps)
+    return scale, b - mean * scale
+
+
+def fold_none(conv):
+    """The (scale, shift) of a layer without BatchNorm: ones, and the bias or zeros."""
+    co, dev = conv.out_channels, conv.weight.device
+    return torch.ones(co, device=dev), conv.bias.float() if conv.bias is not None else torch.zeros(co, device=dev)
+
+
+def cache_attrs(*names):
+    """The attributes CachesWeights._cached keeps for the caches `names`."""
+    return tuple(n + sfx for n in names for sfx in ("", "_key", "_src"))
+
+
 class CachesWeights:
     """Mixin of the modules that keep packed weights / workspaces between calls.  The caches are derived data: they
     are dropped when the parameters are moved or cast (``_apply``: ``.to()`` / ``.cpu()`` / ``.cuda()`` / ``.float()``)
@@ -52,6 +71,16 @@ class CachesWeights:
     def _drop_caches(self):
         for a in self._CACHE_ATTRS:
             self.__dict__.pop(a, None)
+
+    def _cached(self, name, sources, extra, build, head=()):
+        """The cache `name`, rebuilt by build() (under no_grad) when source_key(sources, *extra), behind `head`, is not the
+        key it was built under; kept as the attributes `name`, `name`_key and `name`_src (source_hold)."""
+        key, d = tuple(head) + source_key(sources, *extra), self.__dict__
+        if d.get(name + "_key") != key:
+            with torch.no_grad():
+                value = build()
+            d.update({name: value, name + "_key": key, name + "_src": source_hold(sources)})
+        return d[name]
 
     def cache_tensors(self):
         """Every tensor the caches of this module hold now (packed weights, folded scales, workspaces), nested in dicts,
@@ -97,6 +126,11 @@ def drop_weight_caches(module):
     return module
 
 
+def wino_stack_switch():
+    """DECNET_WINO_STACK=0 turns the fused seven-layer stack off (read per call)."""
+    return os.environ.get("DECNET_WINO_STACK", "1") != "0"
+
+
 def conv_algo(D=None):
     """The Conv3d algorithm of the 216-channel layers.  DECNET_CONV_ALGO = "winograd" (F(2,3) on D, H, W:
     3.4x fewer multiplications than the 27-tap sum), "winograd4" (F(2,3) on D, F(4,3) on H, W: 6x),
@@ -136,31 +170,7 @@ def _ndhwc_view(x):
 
 def _to_ndhwc(x):
     y = _ndhwc_view(x)
-    if y is not None:
-        return y
-    x = x.contiguous()
-    B, C, D, H, W = x.shape
-    out = torch.empty((B, D, H, W, C), dtype=x.dtype, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = _lib.lib().decnet_ncdhw_to_ndhwc(x.data_ptr(), out.data_ptr(), B, C, D, H, W, _stream(x))
-    _lib.check(rc, "decnet_ncdhw_to_ndhwc")
-    return out
-
-
-def costvol_ndhwc(left, right, max_disp, out=None, cost_func="cor"):
-    """[B,C,H,W] x2 -> channels-last cost volume [B,D,H,W,C] ([B,D,H,W,2C] for cost_func="cat")."""
-    _chk("left_feature_map", left)
-    B, C, H, W = left.shape
-    _chk("right_feature_map", right, (B, C, H, W))
-    D = int(max_disp)
-    CO = 2 * C if cost_func == "cat" else C
-    if out is None:
-        out = torch.empty((B, D, H, W, CO), dtype=torch.float32, device=left.device)
-    with torch.cuda.device(left.device):
-        rc = _lib.lib().decnet_costvol_forward_cf(left.data_ptr(), right.data_ptr(), out.data_ptr(),
-                                                  B, C, H, W, D, _lib.COST_FUNC[cost_func], _stream(left))
-    _lib.check(rc, "decnet_costvol_forward_cf")
-    return out
+    return y if y is not None else ops2d.ncdhw_to_ndhwc(x.contiguous())
 
 
 class GetCostVolume(nn.Module):
@@ -194,7 +204,7 @@ class GetCostVolume(nn.Module):
                                           "arange(max_disp) only (submodule.py:389-390)")
         else:
             D = int(kargs["max_disp"])
-        cv = costvol_ndhwc(left_feature_map.contiguous(), right_feature_map.contiguous(), D, cost_func=self.cost_func)
+        cv = ops2d.costvol_forward_cf(left_feature_map.contiguous(), right_feature_map.contiguous(), D, self.cost_func)
         return cv.permute(0, 4, 1, 2, 3)
 
 
@@ -219,7 +229,7 @@ class CostRegNetNoDown(CachesWeights, nn.Module):
     """forward: regularise the cost volume  (submodule.py:608-662)
     args:    x: cost volume, N*C*S*H*W
     return:  regularised cost volume, N*S*H*W"""
-    _CACHE_ATTRS = ("_packed", "_packed_key", "_packed_src", "_ws")
+    _CACHE_ATTRS = cache_attrs("_packed") + ("_ws",)
 
     def __init__(self, in_channels, base_channels, cost_func, down_scale=3):
         super(CostRegNetNoDown, self).__init__()
@@ -263,95 +273,65 @@ class CostRegNetNoDown(CachesWeights, nn.Module):
             ts += [u.conv.weight, u.bn.weight, u.bn.bias, u.bn.running_mean, u.bn.running_var]
         return ts
 
-    def _key(self):
-        return source_key(self._sources(), *[(float(u.bn.eps), bool(u.relu)) for u in self.units()])
-
     def prepare(self, D=None):
         """Repack the 7 wide Conv3d weights to [27,Ci,CoP] on the device and fold eval-mode
         BatchNorm into per-channel scale/shift.  Cached until a parameter (or, through the choice
         of algorithm, the depth D of the volume) changes.  The key is source_key's: a write through ``.data`` after
         the first forward needs ``drop_weight_caches``."""
         algo = conv_algo(D)
-        key = (algo,) + self._key()
-        if self._packed is not None and key == self._packed_key:
-            return self._packed
+        return self._cached("_packed", self._sources(), [(float(u.bn.eps), bool(u.relu)) for u in self.units()],
+                            lambda: self._pack(algo), head=(algo,))
+
+    def _pack(self, algo):
         units = self.units()
         dev = units[0].conv.weight.device
         if dev.type != "cuda":
             raise _lib.DecnetHipError("CostRegNetNoDown parameters are on %s: move the module to "
                                       "the MI355X (no CPU fallback)" % dev)
-        L = _lib.lib()
         packed = []
-        with torch.no_grad(), torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            for i, u in enumerate(units):
-                w = u.conv.weight.detach().float().contiguous()
-                Co, Ci = int(w.shape[0]), int(w.shape[1])
-                # the kernels move channels in 16-byte groups: channel counts that are not a
-                # multiple of 4 (never the case for the shipped 216-channel net) run zero padded
-                cip = (Ci + 3) & ~3
-                cop = (Co + 3) & ~3 if i < 7 else 1
-                if cip != Ci or cop != Co:
-                    wpad = torch.zeros((cop, cip) + tuple(w.shape[2:]), dtype=w.dtype, device=dev)
-                    wpad[:Co, :Ci] = w
-                    w = wpad
-                bn = u.bn
-                eps = float(bn.eps)
-                scale = (bn.weight.detach().float() / torch.sqrt(bn.running_var.float() + eps))
-                shift = bn.bias.detach().float() - bn.running_mean.float() * scale
-                if i < 7 and cop != Co:                 # padded output channels stay exactly 0
-                    scale = torch.cat((scale, torch.ones(cop - Co, device=dev)))
-                    shift = torch.cat((shift, torch.zeros(cop - Co, device=dev)))
-                Co, Ci = cop, cip
-                if i < 7:
-                    CoP = L.decnet_conv3d_packed_cout(Co)
-                    if CoP < 0:
-                        raise _lib.DecnetHipError("Conv3d with %d output channels is not supported "
-                                                  "(<= 224)" % Co)
-                    wp = torch.empty((27, Ci, CoP), dtype=torch.float32, device=dev)
-                    _lib.check(L.decnet_conv3d_pack_weight(w.data_ptr(), wp.data_ptr(), Co, Ci,
-                                                           stream), "decnet_conv3d_pack_weight")
-                    wu = None
-                    if algo in WINO_VARIANT:
-                        var = WINO_VARIANT[algo]
-                        wu = torch.empty(L.decnet_conv3d_wino_weight_floats(Ci, var), dtype=torch.float32,
-                                         device=dev)
-                        _lib.check(L.decnet_conv3d_wino_pack_weight(w.data_ptr(), wu.data_ptr(), Co, Ci, var,
-                                                                    stream), "decnet_conv3d_wino_pack_weight")
-                    packed.append(dict(w=wp, u=wu, scale=scale.contiguous(), shift=shift.contiguous(),
-                                       Ci=Ci, Co=Co, relu=1 if u.relu else 0, keep=w))
-                else:
-                    assert Co == 1
-                    packed.append(dict(w=w, scale=float(scale.item()), shift=float(shift.item()),
-                                       Ci=Ci, Co=1, relu=0))
-            if self.cost_func == "cat":
-                # conv_pre.weight [C,2C,1,1,1] as [Cp][2 Cp] for the zero-padded feature maps of stage0() (left half in
-                # columns [0, C), right half in [Cp, Cp + C)), and as it is for a 2C-channel volume (forward())
-                wpre = self.conv_pre.weight.detach().float().reshape(self.conv_pre.weight.shape[0], -1).contiguous()
-                C = int(wpre.shape[0])
-                cp = (C + 3) & ~3
-                if cp != C:
-                    wp = torch.zeros((cp, 2 * cp), dtype=torch.float32, device=dev)
-                    wp[:C, :C] = wpre[:, :C]
-                    wp[:C, cp:cp + C] = wpre[:, C:]
-                else:
-                    wp = wpre
-                packed[0]["w_pre"], packed[0]["w_pre_true"] = wp, wpre
-        self._packed, self._packed_key, self._packed_src = packed, key, source_hold(self._sources())
+        for i, u in enumerate(units):
+            w = u.conv.weight.detach().float().contiguous()
+            Co, Ci = int(w.shape[0]), int(w.shape[1])
+            # the kernels move channels in 16-byte groups: channel counts that are not a
+            # multiple of 4 (never the case for the shipped 216-channel net) run zero padded
+            cip = (Ci + 3) & ~3
+            cop = (Co + 3) & ~3 if i < 7 else 1
+            if cip != Ci or cop != Co:
+                wpad = torch.zeros((cop, cip) + tuple(w.shape[2:]), dtype=w.dtype, device=dev)
+                wpad[:Co, :Ci] = w
+                w = wpad
+            scale, shift = fold_bn(u.bn)
+            if i < 7 and cop != Co:                 # padded output channels stay exactly 0
+                scale = torch.cat((scale, torch.ones(cop - Co, device=dev)))
+                shift = torch.cat((shift, torch.zeros(cop - Co, device=dev)))
+            if i < 7:
+                wp = ops2d.conv3d_pack_weight(w)
+                wu = ops2d.conv3d_wino_pack_weight(w, WINO_VARIANT[algo]) if algo in WINO_VARIANT else None
+                packed.append(dict(w=wp, u=wu, scale=scale.contiguous(), shift=shift.contiguous(),
+                                   Ci=cip, Co=cop, relu=1 if u.relu else 0, keep=w))
+            else:
+                assert Co == 1
+                packed.append(dict(w=w, scale=float(scale.item()), shift=float(shift.item()), Ci=cip, Co=1, relu=0))
+        if self.cost_func == "cat":
+            # conv_pre.weight [C,2C,1,1,1] as [Cp][2 Cp] for the zero-padded feature maps of stage0() (left half in
+            # columns [0, C), right half in [Cp, Cp + C)), and as it is for a 2C-channel volume (forward())
+            wpre = self.conv_pre.weight.detach().float().reshape(self.conv_pre.weight.shape[0], -1).contiguous()
+            C = int(wpre.shape[0])
+            cp = (C + 3) & ~3
+            if cp != C:
+                wp = torch.zeros((cp, 2 * cp), dtype=torch.float32, device=dev)
+                wp[:C, :C] = wpre[:, :C]
+                wp[:C, cp:cp + C] = wpre[:, C:]
+            else:
+                wp = wpre
+            packed[0]["w_pre"], packed[0]["w_pre_true"] = wp, wpre
         return packed
 
-    def _workspace(self, dev, n):
-        ws = self._ws.get(dev)
-        if ws is None or ws[0].numel() < n:
-            ws = [torch.empty(n, dtype=torch.float32, device=dev) for _ in range(3)]
-            self._ws[dev] = ws
-        return ws
-
-    def _scratch(self, dev, n):
-        t = self._ws.get(("scratch", dev))
+    def _grow(self, key, n):
+        """The grow-only fp32 workspace `key` = (what, ..., device): at least n floats."""
+        t = self._ws.get(key)
         if t is None or t.numel() < n:
-            t = torch.empty(n, dtype=torch.float32, device=dev)
-            self._ws[("scratch", dev)] = t
+            t = self._ws[key] = torch.empty(n, dtype=torch.float32, device=key[-1])
         return t
 
     def run_ndhwc(self, x, want_reg=True, want_pred=True):
@@ -368,112 +348,53 @@ class CostRegNetNoDown(CachesWeights, nn.Module):
         if self.cost_func == "cat":                      # submodule.py:651-652: x = conv_pre(x), 2C -> C channels
             if C != 2 * c_true:
                 raise ValueError("cost volume has %d channels, module expects %d" % (C, 2 * c_true))
-            y = torch.empty((B, D, H, W, c_true), dtype=torch.float32, device=x.device)
-            with torch.cuda.device(x.device):
-                rc = _lib.lib().decnet_conv3d_pointwise(x.data_ptr(), P[0]["w_pre_true"].data_ptr(), y.data_ptr(), B, C,
-                                                        c_true, D * H * W, C, 1, _stream(x))
-            _lib.check(rc, "decnet_conv3d_pointwise")
-            x, C = y, c_true
+            x, C = ops2d.conv3d_pointwise(x, P[0]["w_pre_true"]), c_true
         if C == c_true and P[0]["Ci"] != C:             # channel count not a multiple of 4: zero pad
             x = torch.nn.functional.pad(x, (0, P[0]["Ci"] - C))
             C = P[0]["Ci"]
         if P[0]["Ci"] != C:
             raise ValueError("cost volume has %d channels, module expects %d" % (C, c_true))
-        L = _lib.lib()
-        dev = x.device
-        a, b, c = self._workspace(dev, B * D * H * W * C)
-        reg = torch.empty((B, D, H, W), dtype=torch.float32, device=dev) if want_reg else None
-        pred = torch.empty((B, H, W), dtype=torch.float32, device=dev)
-
-        wino = algo in WINO_VARIANT
-        wsp = None
-        if wino:
-            var = WINO_VARIANT[algo]
-            n = L.decnet_conv3d_wino_workspace_floats(B, D, H, W, C, C, var)
-            wsp = self._ws.get(("wino", dev))
-            if wsp is None or wsp.numel() < n:
-                wsp = torch.empty(n, dtype=torch.float32, device=dev)
-                self._ws[("wino", dev)] = wsp
+        dev, dims = x.device, (B, D, H, W)
+        a, b, c = (self._grow(("act", i, dev), B * D * H * W * C) for i in range(3))
+        reg = torch.empty(dims, dtype=torch.float32, device=dev) if want_reg else None
+        var = WINO_VARIANT.get(algo)
+        wsp = None if var is None else self._grow(("wino", dev), ops2d.size("conv3d_wino_workspace_floats", *dims, C, C, var))
 
         def conv(i, src, dst, res=None):
             p = P[i]
-            r = res.data_ptr() if res is not None else None
-            if wino:
-                rc = L.decnet_conv3d_wino_bn_act(src.data_ptr(), p["u"].data_ptr(), p["scale"].data_ptr(),
-                                                 p["shift"].data_ptr(), r, dst.data_ptr(), wsp.data_ptr(),
-                                                 B, D, H, W, p["Ci"], p["Co"], p["relu"], var, st)
-                _lib.check(rc, "decnet_conv3d_wino_bn_act[%d]" % i)
-            else:
-                rc = L.decnet_conv3d_bn_act(src.data_ptr(), p["w"].data_ptr(), p["scale"].data_ptr(),
-                                            p["shift"].data_ptr(), r, dst.data_ptr(), B, D, H, W,
-                                            p["Ci"], p["Co"], p["relu"], st)
-                _lib.check(rc, "decnet_conv3d_bn_act[%d]" % i)
+            ops2d.conv3d_bn_act(src, p["w" if wsp is None else "u"], p["scale"], p["shift"], res, dst, dims, p["Ci"], p["Co"],
+                                p["relu"], wsp, var)
 
-        with torch.cuda.device(dev):
-            st = _stream(x)
-            # CostRegNetNoDown.forward submodule.py:650-662
-            if not self._run_stack(L, P, x, c, B, D, H, W, C, algo, st):
-                conv(0, x, a)
-                conv(1, a, c)                 # c = output0
-                conv(2, c, a)
-                conv(3, a, b)
-                conv(4, b, a, res=c)          # conv1(output0) + output0
-                conv(5, a, b)
-                conv(6, b, c)
-            p = P[7]
-            regp = reg.data_ptr() if reg is not None else None
-            need = L.decnet_conv3d_cout1_workspace_floats(B, D, H, W)
-            if p["Ci"] <= 256 and D <= 256:
-                t = a if a.numel() >= need else self._scratch(dev, need)     # a is free by now
-                rc = L.decnet_conv3d_cout1_softargmax_ws(c.data_ptr(), p["w"].data_ptr(), p["scale"], p["shift"],
-                                                         regp, pred.data_ptr(), t.data_ptr(), B, D, H, W,
-                                                         p["Ci"], st)
-                _lib.check(rc, "decnet_conv3d_cout1_softargmax_ws")
-            else:
-                rc = L.decnet_conv3d_cout1_softargmax(c.data_ptr(), p["w"].data_ptr(), p["scale"], p["shift"],
-                                                      regp, pred.data_ptr(), B, D, H, W, p["Ci"], st)
-                _lib.check(rc, "decnet_conv3d_cout1_softargmax")
+        # CostRegNetNoDown.forward submodule.py:650-662
+        if not self._run_stack(P, x, c, dims, C, var):
+            conv(0, x, a)
+            conv(1, a, c)                 # c = output0
+            conv(2, c, a)
+            conv(3, a, b)
+            conv(4, b, a, res=c)          # conv1(output0) + output0
+            conv(5, a, b)
+            conv(6, b, c)
+        p, t = P[7], None
+        if p["Ci"] <= 256 and D <= 256:
+            need = ops2d.size("conv3d_cout1_workspace_floats", B, D, H, W)
+            t = a if a.numel() >= need else self._grow(("scratch", dev), need)     # a is free by now
+        pred = ops2d.conv3d_cout1_softargmax(c, p["w"], p["scale"], p["shift"], dims, p["Ci"], reg=reg, ws=t)
         return reg, (pred if want_pred else None)
 
-    def _run_stack(self, L, P, x, out, B, D, H, W, C, algo, st):
+    def _run_stack(self, P, x, out, dims, C, var):
         """The seven C -> C units as ONE fused stack (decnet_conv3d_wino_stack_bn_act: the activations between the
         layers stay on chip); False when the shape is not covered (the caller then runs the layers one by one).
         DECNET_WINO_STACK=0 turns it off."""
-        if algo not in WINO_VARIANT or os.environ.get("DECNET_WINO_STACK", "1") == "0":
+        if var is None or not wino_stack_switch() or any(not p["relu"] or p["Ci"] != C or p["Co"] != C for p in P[:7]):
             return False
-        if any(not p["relu"] or p["Ci"] != C or p["Co"] != C for p in P[:7]):
-            return False
-        var = WINO_VARIANT[algo]
-        n = L.decnet_conv3d_wino_stack_workspace_floats(B, D, H, W, C, var)
+        n = ops2d.size("conv3d_wino_stack_workspace_floats", *dims, C, var)
         if n == 0:
             return False
-        dev = x.device
-        wsp = self._ws.get(("wino", dev))
-        if wsp is None or wsp.numel() < n:
-            wsp = torch.empty(n, dtype=torch.float32, device=dev)
-            self._ws[("wino", dev)] = wsp
-        import ctypes
-        arr = ctypes.c_void_p * 7
-        u, sc, sh = (arr(*[P[i][k].data_ptr() for i in range(7)]) for k in ("u", "scale", "shift"))
-        rc = L.decnet_conv3d_wino_stack_bn_act(x.data_ptr(), u, sc, sh, 7, 1, 4, out.data_ptr(), wsp.data_ptr(),
-                                               B, D, H, W, C, var, st)
-        if rc == _lib.UNSUPPORTED:
-            return False
-        _lib.check(rc, "decnet_conv3d_wino_stack_bn_act")
-        return True
+        return ops2d.conv3d_wino_stack_bn_act(x, P[:7], 1, 4, out, self._grow(("wino", x.device), n), dims, C, var)
 
     def forward(self, x):
         reg, _ = self.run_ndhwc(_to_ndhwc(x), want_reg=True, want_pred=False)
         return reg
-
-    def costvol_buffer(self, dev, B, D, H, W, C):
-        """The channels-last cost-volume buffer of this module for one shape on one device."""
-        key = ("cv", dev)
-        cv = self._ws.get(key)
-        if cv is None or tuple(cv.shape) != (B, D, H, W, C):
-            cv = torch.empty((B, D, H, W, C), dtype=torch.float32, device=dev)
-            self._ws[key] = cv
-        return cv
 
     def stage0(self, left_feature_map, right_feature_map, max_disp, return_reg=False):
         """SparseDenseNetRefinementMask.forward :127-137 in one call: cost volume (stage-0 ``arange``
@@ -483,8 +404,7 @@ class CostRegNetNoDown(CachesWeights, nn.Module):
                                                           right_feature_map.requires_grad)):
             raise NotImplementedError("CostRegNetNoDown on gfx950 is inference-only: call "
                                       ".eval() and run under torch.no_grad()")
-        left = left_feature_map.contiguous()
-        right = right_feature_map.contiguous()
+        left, right = left_feature_map.contiguous(), right_feature_map.contiguous()
         _chk("left_feature_map", left)
         if left.shape[1] % 4:                           # see prepare()
             padc = (0, 0, 0, 0, 0, 4 - left.shape[1] % 4)
@@ -503,9 +423,7 @@ class CostRegNetNoDown(CachesWeights, nn.Module):
             # does (submodule.py:624-648); a unit built with relu=False needs the per-layer path (forward())
             raise _lib.DecnetHipError("decnet_stage0_forward: a Conv3dUnit without ReLU is not covered by the "
                                       "single-entry stage-0 path; use CostRegNetNoDown.forward")
-        L = _lib.lib()
-        dev = left.device
-        variant = WINO_VARIANT.get(algo, 3)
+        dev, variant = left.device, WINO_VARIANT.get(algo, 3)
         pk = self._ws.get(("s0params", dev))
         if pk is None or pk[0] is not P or pk[1] != variant:
             sp = _lib.Stage0Params()
@@ -513,25 +431,13 @@ class CostRegNetNoDown(CachesWeights, nn.Module):
                 sp.w[i] = P[i]["u"].data_ptr() if variant <= 2 else P[i]["w"].data_ptr()
                 sp.scale[i], sp.shift[i] = P[i]["scale"].data_ptr(), P[i]["shift"].data_ptr()
             sp.w_last, sp.scale_last, sp.shift_last = P[7]["w"].data_ptr(), P[7]["scale"], P[7]["shift"]
-            pk = (P, variant, sp)
-            self._ws[("s0params", dev)] = pk
-        cf = _lib.COST_FUNC[self.cost_func]
-        n = L.decnet_stage0_cf_workspace_floats(B, C, H, W, D, variant, cf)
+            pk = self._ws[("s0params", dev)] = (P, variant, sp)
+        n = ops2d.size("stage0_cf_workspace_floats", B, C, H, W, D, variant, _lib.COST_FUNC[self.cost_func])
         if n == 0:
             raise _lib.DecnetHipError("decnet_stage0_forward_cf: shape not supported")
-        ws = self._ws.get(("s0", dev))
-        if ws is None or ws.numel() < n:
-            ws = torch.empty(n, dtype=torch.float32, device=dev)
-            self._ws[("s0", dev)] = ws
         reg = torch.empty((B, D, H, W), dtype=torch.float32, device=dev) if return_reg else None
-        pred = torch.empty((B, H, W), dtype=torch.float32, device=dev)
-        import ctypes
-        with torch.cuda.device(dev):
-            rc = L.decnet_stage0_forward_cf(left.data_ptr(), right.data_ptr(), ctypes.byref(pk[2]),
-                                            P[0]["w_pre"].data_ptr() if self.cost_func == "cat" else None, ws.data_ptr(),
-                                            reg.data_ptr() if reg is not None else None, pred.data_ptr(),
-                                            B, C, H, W, D, variant, cf, _stream(left))
-        _lib.check(rc, "decnet_stage0_forward_cf")
+        pred = ops2d.stage0_forward_cf(left, right, pk[2], P[0]["w_pre"] if self.cost_func == "cat" else None,
+                                       self._grow(("s0", dev), n), D, variant, self.cost_func, reg=reg)
         return (pred, reg) if return_reg else pred
 
     def stage0_buffers(self, dev, B, C, H, W, D):
@@ -550,12 +456,7 @@ def disparity_regression(cost_vol, disp_samples):
     B, S, H, W = cost_vol.shape
     disp_samples = disp_samples.expand(B, S, H, W).contiguous()
     _chk("disp_samples", disp_samples, (B, S, H, W))
-    pred = torch.empty((B, H, W), dtype=torch.float32, device=cost_vol.device)
-    with torch.cuda.device(cost_vol.device):
-        rc = _lib.lib().decnet_disparity_regression(cost_vol.data_ptr(), disp_samples.data_ptr(),
-                                                    pred.data_ptr(), B, S, H, W, _stream(cost_vol))
-    _lib.check(rc, "decnet_disparity_regression")
-    return pred
+    return ops2d.disparity_regression(cost_vol, disp_samples)
 
 
 class Stage0(nn.Module):
