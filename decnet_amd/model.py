@@ -21,6 +21,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops2d
+from .conv2d_grad import Conv2dSmallFunction, hip_grad_enabled
 from ._lib import DecnetHipError, UNSUPPORTED
 from .ops import spamatvar_forward, spamatvar_forward_bits
 from .stage0 import (CachesWeights, CostRegNetNoDown, Stage0, cache_attrs, drop_weight_caches, fold_bn, fold_none,  # noqa: F401
@@ -120,14 +121,16 @@ class Unit(CachesWeights, nn.Module):
             return None
         return self._route(x.shape[0], x.shape[-2], x.shape[-1], parts)
 
-    def _route(self, B, H, W, parts=None):
+    def _route(self, B, H, W, parts=None, switches=None):
         """The table behind _hip_kind, a function of the layer, the input size, the number of concatenated parts (None:
-        one tensor) and the two switches alone: no tensor, no GPU.  (No threshold depends on B today.)"""
+        one tensor) and the two switches alone: no tensor, no GPU.  (No threshold depends on B today.)
+        switches: (conv2d_switch(), mfma_switch()) to decide with, None: as the environment has them."""
         c, hw = self.conv, H * W
         ci, co, tr = c.in_channels, c.out_channels, isinstance(c, nn.ConvTranspose2d)
-        if not conv2d_switch() or (parts is not None and (parts > 6 or not _same_padded(c))):  # (the `cat` entries are
+        conv_on, mfma_on = (conv2d_switch(), mfma_switch()) if switches is None else switches
+        if not conv_on or (parts is not None and (parts > 6 or not _same_padded(c))):          # (the `cat` entries are
             return None                                                                        # "conv"'s and "mfma"'s)
-        if mfma_switch():
+        if mfma_on:
             # many channels: the bf16x3 matrix-core kernel (csrc/conv2d_mfma.hip) where the image gives it enough
             # workgroups (>= 4096 pixels, e.g. the 60 x 108 level; at 20 x 36 the library's kernels win)
             # (round 3: also 9..23 outputs from >= 16 inputs.  The 20 x 36 level stays on the library: measured with the
@@ -154,6 +157,43 @@ class Unit(CachesWeights, nn.Module):
         if tr:
             return "deconv" if _deconv_k3s3(c) else None
         return "conv" if _same_padded(c) else None
+
+    def _grad_route(self, B, H, W, parts=None):
+        """"conv" when the unit's backward runs on the HIP kernels under ``hip_grad()`` (conv2d_grad.Conv2dSmallFunction),
+        else None: the layers _route sends to "conv" with the switches at their defaults, up to 24 input channels (dx is
+        the same kernel with the channel roles swapped), from 256 pixels.  Pure, like _route."""
+        if self.conv.in_channels > 24 or H * W < 256:
+            return None
+        return "conv" if self._route(B, H, W, parts, switches=(True, True)) == "conv" else None
+
+    def _forward_grad(self, x):
+        """The forward under ``hip_grad()`` with autograd on: the same kernels, the backward recorded on ours.  None
+        where the unit, the input or the shape is not covered (the caller then goes on as it always did)."""
+        xs = tuple(x) if isinstance(x, (tuple, list)) else (x,)
+        x0, c = xs[0], self.conv
+        if not (x0.is_cuda and c.weight.dtype == torch.float32) or any(
+                t.dim() != 4 or t.dtype != torch.float32 or t.device != x0.device or t.shape[0] != x0.shape[0] or
+                t.shape[2:] != x0.shape[2:] for t in xs):
+            return None
+        parts = len(xs) if isinstance(x, (tuple, list)) else None
+        if self._grad_route(x0.shape[0], x0.shape[-2], x0.shape[-1], parts) is None:
+            return None
+        if self.bn is not None:                                         # differentiable (fold_bn's arithmetic)
+            scale, shift = fold_bn(self.bn)
+        else:
+            scale, shift = fold_none(c)
+        n_tally = None if TALLY is None else len(TALLY)
+        if TALLY is not None:
+            _tally(self, "conv_grad", x)
+        try:
+            return Conv2dSmallFunction.apply(self._folded(), c.kernel_size[0], c.dilation[0], bool(self.relu), c.weight,
+                                             scale, shift, *xs)
+        except DecnetHipError as e:                     # the grid limits of the forward kernel: the library takes it
+            if e.code != UNSUPPORTED:
+                raise
+            if n_tally is not None:
+                del TALLY[n_tally:]
+            return None
 
     def _sources(self):
         c, bn = self.conv, self.bn
@@ -239,6 +279,10 @@ class Unit(CachesWeights, nn.Module):
         return ops2d.conv2d_bn_act(x.contiguous(), *wss, ci, k, dil, relu, out=out)
 
     def forward(self, x):
+        if hip_grad_enabled() and not self.training and torch.is_grad_enabled():
+            y = self._forward_grad(x)
+            if y is not None:
+                return y
         kind = self._hip_kind(x)
         if kind is not None:
             try:

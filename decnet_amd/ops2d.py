@@ -115,6 +115,39 @@ def conv2d_cat_epilogue(xs, w, scale, shift, cin, k, dil, relu, epi, ea, eb=None
     return _conv2d_cat("decnet_conv2d_cat_epilogue", _F32, xs, w, scale, shift, cin, k, dil, relu, out, int(epi), ea, eb)
 
 
+_WGRAD_FLOATS = {}
+
+
+def conv2d_wgrad(xs, gy, y, k, dil):
+    """Weight-gradient reduction of a few-channel stride-1 unit (decnet_conv2d_wgrad, csrc/conv2d_grad.hip): xs the parts
+    [B,c_i,H,W] of the input, gy [B,Cout,H,W], y the unit's output (the ReLU mask y > 0) or None -> (G [Cout,Cin,k,k],
+    gsum [Cout], gm = gy * [y > 0] [B,Cout,H,W]; gy itself without y).  The workspace comes from torch.empty, its size from
+    the library's query, cached per shape."""
+    B, Co, H, W = _chk("gy", gy).shape
+    if y is not None:
+        _chk("y", y, (B, Co, H, W))
+    for t in xs:
+        _chk("input part", t, (B, t.shape[1], H, W))
+    cins, n = [int(t.shape[1]) for t in xs], len(xs)
+    cin, k, dil = sum(cins), int(k), int(dil)
+    key = (B, cin, Co, H, W, k)
+    nws = _WGRAD_FLOATS.get(key)
+    if nws is None:
+        nws = _WGRAD_FLOATS[key] = int(size("conv2d_wgrad_workspace_floats", *key))
+    if nws == 0:
+        raise _lib.DecnetHipError("decnet_conv2d_wgrad does not cover B %d, Cin %d, Cout %d, %d x %d, k %d"
+                                  % (B, cin, Co, H, W, k))
+    dev = gy.device
+    G = torch.empty((Co, cin, k, k), dtype=_F32, device=dev)
+    gsum = torch.empty((Co,), dtype=_F32, device=dev)
+    gm = gy if y is None else torch.empty_like(gy)
+    ws = torch.empty(nws, dtype=_F32, device=dev)                      # torch allocations are 16-byte aligned
+    _call("decnet_conv2d_wgrad", gy, (ctypes.c_void_p * n)(*[t.data_ptr() for t in xs]), (ctypes.c_int * n)(*cins), n,
+          gy.data_ptr(), None if y is None else y.data_ptr(), None if y is None else gm.data_ptr(), G.data_ptr(),
+          gsum.data_ptr(), ws.data_ptr(), nws, B, Co, H, W, k, dil)
+    return G, gsum, gm
+
+
 def bias_act_inplace(x, b, relu):
     B, Co, H, W = _chk("x", x).shape
     _call("decnet_bias_act_inplace", x, x.data_ptr(), _chk("bias", b, (Co,)).data_ptr(), B, Co, H, W, relu)

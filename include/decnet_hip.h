@@ -382,6 +382,26 @@ size_t decnet_deconv2d_mfma_packed_bytes(int Cin, int Cout);
 int decnet_deconv2d_mfma_pack_weight(const float *w, void *w_packed, int Cin, int Cout, void *stream);
 int decnet_deconv2d_mfma_k3s3_bn_act(const float *x, const void *w_packed, const float *scale, const float *shift,
                                      float *y, int B, int Cin, int Cout, int H, int W, int relu, void *stream);
+/* Weight gradient of decnet_conv2d_cat_bn_act with frozen BatchNorm (csrc/conv2d_grad.hip): for
+ * y = act(conv(x, w) * scale + shift) and the upstream gradient gy, gm = gy * [y > 0] (gm = gy without ReLU: y NULL) and
+ *   G[co][ci][ky][kx] = sum_{b,y,x} gm[b][co][y][x] * x[b][ci][y + (ky - k/2) d][x + (kx - k/2) d]   (zeros outside)
+ *   gsum[co]          = sum_{b,y,x} gm[b][co][y][x]
+ * so that dW = scale * G, dscale = <w, G>, dshift = gsum; dx is decnet_conv2d_bn_act itself on gm with the weights
+ * w'[ci][co][ky][kx] = w[co][ci][k-1-ky][k-1-kx] * scale[co].
+ *   xs, cins, nseg   the input as for decnet_conv2d_cat_bn_act (Cin = sum of cins <= 24)
+ *   gy, y            [B,Cout,H,W]; y: the layer's OUTPUT (read only as the mask y > 0), NULL for a layer without ReLU
+ *   gm               [B,Cout,H,W], written in full; may be NULL when y is NULL
+ *   G, gsum          [Cout,Cin,k,k], [Cout], written in full
+ *   workspace        decnet_conv2d_wgrad_workspace_floats(B, Cin, Cout, H, W, k) floats (0: shape not covered), 16-byte
+ *                    aligned (else DECNET_ERR_MISALIGNED); fewer floats than the query: DECNET_ERR_BAD_SHAPE
+ * Every other buffer is accepted at any float alignment.  Deterministic: workgroups write partial sums (fp32 chains of at
+ * most 512 terms) into the workspace, a second launch adds them in a fixed order in float64 and rounds once; no atomics,
+ * no allocation, no synchronisation (capturable).  DECNET_ERR_UNSUPPORTED: k not 1 or 3, Cout > 24, Cin > 24, nseg > 6,
+ * H or B > 65535, W > 2^28.  Nothing is launched on any refusal. */
+size_t decnet_conv2d_wgrad_workspace_floats(int B, int Cin, int Cout, int H, int W, int k);
+int decnet_conv2d_wgrad(const float *const *xs, const int *cins, int nseg, const float *gy, const float *y, float *gm,
+                        float *G, float *gsum, float *workspace, size_t workspace_floats, int B, int Cout, int H,
+                        int W, int k, int dilation, void *stream);
 /* Refinement.get_warped_feats_by_homgrp (submodule.py:719-745): out[b,c,y,x] = bilinear(right[b,c];
  * (x - disp[b,y,x]) * W/(W-1) - 0.5, y * H/(H-1) - 0.5), zero padding.  right,out [B,C,H,W], disp [B,H,W]. */
 int decnet_warp_disparity(const float *right, const float *disp, float *out, int B, int C, int H, int W,
