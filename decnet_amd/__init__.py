@@ -6,7 +6,9 @@
 * StereoEngine: uint8 pairs in, uint16 disparity out -- the whole network as one HIP graph per shape, copies pipelined
 * Loss: the multi-stage training loss (reference modules/loss.py), one fused kernel pair per pyramid level
 * hip_grad(): opt-in backward of the few-channel stride-1 conv units with frozen BatchNorm (Conv2dSmallFunction): the
-  weight gradient as a deterministic fp32 matrix-core reduction, dx on the forward kernel with flipped weights
+  weight gradient as a deterministic fp32 matrix-core reduction, dx on the forward kernel with flipped weights; and of
+  the full-resolution tail (WarpDisparityFunction, Unfold3CatFunction, DynamicUpsample3Function, SigmoidBlendFunction):
+  the inference entries forward, fixed-order gathers backward
 
 Host side is Python on PyTorch-ROCm (device memory + streams only); all arithmetic runs in
 hand-written HIP kernels behind the C ABI of include/decnet_hip.h.  No CPU fallback.
@@ -20,10 +22,13 @@ from .ops import spamatvar_forward, spamatvar_forward_bits  # noqa: F401
 from .engine import StereoEngine  # noqa: F401
 from .loss import Loss, StageLossFunction  # noqa: F401
 from .conv2d_grad import Conv2dSmallFunction, hip_grad, hip_grad_enabled  # noqa: F401
+from .tail_grad import (DynamicUpsample3Function, SigmoidBlendFunction, Unfold3CatFunction,  # noqa: F401
+                        WarpDisparityFunction)
 from .stage0 import (CostRegNetNoDown, GetCostVolume, Stage0, disparity_regression,  # noqa: F401
                      drop_weight_caches, get_disp_samples)
 
 __all__ = ["SpaMat", "SpaVar", "SpaMatFunction", "SpaVarFunction", "spamatvar_forward", "spamatvar_forward_bits",
            "GetCostVolume", "CostRegNetNoDown", "disparity_regression", "get_disp_samples",
            "Stage0", "DecnetHipError", "version", "drop_weight_caches", "StereoEngine", "Loss",
-           "StageLossFunction", "Conv2dSmallFunction", "hip_grad", "hip_grad_enabled"]
+           "StageLossFunction", "Conv2dSmallFunction", "hip_grad", "hip_grad_enabled", "WarpDisparityFunction",
+           "Unfold3CatFunction", "DynamicUpsample3Function", "SigmoidBlendFunction"]

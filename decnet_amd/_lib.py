@@ -53,6 +53,12 @@ SIGNATURES = {
     "decnet_conv2d_k3s3_bn_act": [_P] * 5 + [_I] * 6 + [_P],
     "decnet_bias_act_inplace": [_P, _P] + [_I] * 5 + [_P],
     "decnet_unfold3_cat": [_P] * 3 + [_I] * 4 + [_P],
+    "decnet_warp_disparity_backward": [_P] * 5 + [_I] * 4 + [_P],
+    "decnet_dynamic_upsample3_backward_workspace_floats": [_I] * 3,
+    "decnet_dynamic_upsample3_backward": [_P] * 6 + [_Z] + [_I] * 3 + [_P],
+    "decnet_fold3": [_P, _P] + [_I] * 4 + [_P],
+    "decnet_sigmoid_blend": [_P] * 4 + [_Z, _P],
+    "decnet_sigmoid_blend_backward": [_P] * 7 + [_Z, _P],
     "decnet_s2d3_pad1": [_P, _P] + [_I] * 4 + [_P],
     "decnet_detail_mask": [_P] * 6 + [_F] * 3 + [_P] * 3 + [_I] * 3 + [_P],
     "decnet_conv2d_cat_bn_act": [_P, _P, _I, _P, _P, _P, _P] + [_I] * 7 + [_P],

@@ -12,7 +12,8 @@ gradient gy and gm = gy * [y > 0] (gm = gy without ReLU):
 ``scale`` and ``shift`` enter the Function as differentiable torch expressions of the BatchNorm parameters, so autograd
 carries dscale / dshift on to ``bn.weight``, ``bn.bias`` and ``conv.bias``; nothing flows to the running statistics.
 
-``hip_grad()`` switches the path on for the calling thread (default: off -- ``model.Unit`` then behaves as before).
+``hip_grad()`` switches the path on for the calling thread (default: off -- ``model.Unit`` then behaves as before).  The
+same switch puts the warp, the dynamic upsampling and SoftAttention's blend on their HIP Functions (tail_grad.py).
 Out of scope: training-mode BatchNorm, the stride-3 / transposed / matrix-core layers, stage 0, double backward.
 """
 import contextlib

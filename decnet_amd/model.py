@@ -22,6 +22,7 @@ import torch.nn.functional as F
 
 from . import ops2d
 from .conv2d_grad import Conv2dSmallFunction, hip_grad_enabled
+from .tail_grad import DynamicUpsample3Function, SigmoidBlendFunction, Unfold3CatFunction, WarpDisparityFunction
 from ._lib import DecnetHipError, UNSUPPORTED
 from .ops import spamatvar_forward, spamatvar_forward_bits
 from .stage0 import (CachesWeights, CostRegNetNoDown, Stage0, cache_attrs, drop_weight_caches, fold_bn, fold_none,  # noqa: F401
@@ -72,6 +73,27 @@ def hip_gate(t, training=False, fp32=True, switch=True):
     one), and -- terms a site can leave out or check elsewhere -- float32 and DECNET_CONV2D=hip."""
     return (not training and t.is_cuda and not torch.is_grad_enabled() and (not fp32 or t.dtype == torch.float32) and
             (not switch or conv2d_switch()))
+
+
+def tail_grad_gate(*ts):
+    """The tail Functions of tail_grad.py may take these tensors: inside ``hip_grad()`` with autograd on, all on the GPU
+    in float32.  (CPU tensors: False before any library lookup.)"""
+    return (hip_grad_enabled() and torch.is_grad_enabled() and
+            all(t.is_cuda and t.dtype == torch.float32 for t in ts))
+
+
+def tail_grad_route(op, B, C, H, W, s=3, fea_hw=None):
+    """Whether `op` ("warp", "unfold", "upsample") runs as its tail_grad Function under ``hip_grad()``: the shape limits
+    of the inference route of the same op, decided with the switches at their defaults (as Unit._grad_route).  A function
+    of sizes alone: no tensor, no GPU.  warp: right [B,C,H,W]; unfold: fea [B,C,*fea_hw], disp [B,H,W], down-scale s;
+    upsample: disp [B,H,W] (C is not looked at)."""
+    if op == "warp":
+        return H > 1 and W > 1 and H <= 65535
+    if op == "unfold":
+        return s == 3 and H <= 65535 and B * (C + 1) <= 65535 and tuple(fea_hw) == (3 * H, 3 * W)
+    if op == "upsample":
+        return s == 3 and H <= 65535
+    raise ValueError("no such op: %s" % op)
 
 
 def _same_padded(c):
@@ -517,12 +539,17 @@ class DynamicUpsampling(nn.Module):
     def forward(self, disp, fea):
         B, h, w = disp.shape
         s2 = self.s ** 2
-        if (self.s == 3 and hip_gate(fea) and h <= 65535 and B * (fea.shape[1] + 1) <= 65535 and
+        grad = tail_grad_gate(disp, fea)                # under hip_grad(): the same entries, the backward on ours
+        if grad and tail_grad_route("unfold", B, fea.shape[1], h, w, self.s, fea.shape[-2:]):
+            wts = Unfold3CatFunction.apply(fea, disp)
+        elif (self.s == 3 and hip_gate(fea) and h <= 65535 and B * (fea.shape[1] + 1) <= 65535 and
                 tuple(fea.shape[-2:]) == (3 * h, 3 * w)):       # cat(disp, unfold(fea)) as one pass (csrc/unfold.hip)
             wts = ops2d.unfold3_cat(fea.contiguous(), disp.contiguous())
         else:
             wts = torch.cat((disp.unsqueeze(1), F.unfold(fea, self.s, stride=self.s).view(B, -1, h, w)), 1)
         logits = self.weight_learning(wts)
+        if grad and tail_grad_gate(logits) and tail_grad_route("upsample", B, 81, h, w, self.s):
+            return DynamicUpsample3Function.apply(logits, disp)
         if self.s == 3 and hip_gate(logits) and h <= 65535:
             return ops2d.dynamic_upsample3(logits.contiguous(), disp.contiguous())
         wts = F.softmax(logits.view(B, s2, 9, h * w), 2)
@@ -549,6 +576,10 @@ class SoftAttention(nn.Module):
         of the three convolution launches."""
         parts = (fea, dense.unsqueeze(1), sparse.unsqueeze(1), mask.unsqueeze(1), var.unsqueeze(1))
         u0, u1, u2 = self.conv[0], self.conv[1], self.conv[2]
+        if not self.training and u2.conv.out_channels == 1 and not u2.relu and tail_grad_gate(*parts):
+            y = self._fuse_grad(parts, dense, sparse)
+            if y is not None:
+                return y
         k0 = u0._hip_kind(parts)
         if k0 in ("conv", "mfma") and u2.conv.out_channels == 1 and not u2.relu:
             if k0 == "conv":
@@ -563,11 +594,35 @@ class SoftAttention(nn.Module):
         soft = self(parts[:4] + (-var.unsqueeze(1),)).squeeze(1)
         return dense * (1 - soft) + soft * sparse
 
+    def _fuse_grad_route(self, B, H, W):
+        """Whether fuse() under ``hip_grad()`` runs its three units as Conv2dSmallFunctions (the variance negated as a
+        tensor: fma(-v, w, acc) and fma(v, -w, acc) are the same bits) and the blend as SigmoidBlendFunction.  Pure."""
+        u0, u1, u2 = self.conv[0], self.conv[1], self.conv[2]
+        return (u2.conv.out_channels == 1 and not u2.relu and u0._grad_route(B, H, W, 5) == "conv" and
+                u1._grad_route(B, H, W) == "conv" and u2._grad_route(B, H, W) == "conv")
+
+    def _fuse_grad(self, parts, dense, sparse):
+        """fuse() on the route of _fuse_grad_route; None where it does not hold (the caller goes on as it always did)."""
+        B, _, H, W = parts[0].shape
+        if any(u.training for u in self.conv) or not self._fuse_grad_route(B, H, W):
+            return None
+        n_tally = None if TALLY is None else len(TALLY)
+        t = parts[:4] + (-parts[4],)
+        for u in self.conv:
+            t = u._forward_grad(t)
+            if t is None:                               # a grid limit of the forward kernel: the usual route, from the start
+                if n_tally is not None:
+                    del TALLY[n_tally:]
+                return None
+        return SigmoidBlendFunction.apply(t.squeeze(1), dense, sparse)
+
 
 def warp_by_disparity(right, disp):
     """Refinement.get_warped_feats_by_homgrp (submodule.py:719-745): the same stretched,
     half-pixel-shifted bilinear warp as stage 0, one disparity per pixel."""
     B, C, H, W = right.shape
+    if tail_grad_gate(right, disp) and tail_grad_route("warp", B, C, H, W):
+        return WarpDisparityFunction.apply(right, disp)
     if hip_gate(right) and H > 1 and W > 1 and H <= 65535:
         return ops2d.warp_disparity(right.contiguous(), disp.contiguous())
     ys, xs = torch.meshgrid(torch.arange(H, dtype=right.dtype, device=right.device),

@@ -209,6 +209,74 @@ def warp_disparity(right, disp, out=None):
     return _run("decnet_warp_disparity", (right, disp), out, (B, C, H, W), B, C, H, W)
 
 
+# ---- the full-resolution tail under hip_grad() (csrc/tail_grad.hip; the Functions are in tail_grad.py) -------------------
+def warp_disparity_backward(right, disp, gout, want_right=True, want_disp=True):
+    """-> (g_right [B,C,H,W] or None, g_disp [B,H,W] or None).  A width beyond the g_right kernel's LDS plan raises
+    DecnetHipError with code UNSUPPORTED (nothing launched): ask for g_disp alone then."""
+    B, C, H, W = _chk("right", right).shape
+    _chk("disp", disp, (B, H, W))
+    _chk("gout", gout, (B, C, H, W))
+    if not (want_right or want_disp):
+        return None, None
+    gr = torch.empty_like(right) if want_right else None
+    gd = torch.empty_like(disp) if want_disp else None
+    _call("decnet_warp_disparity_backward", right, right.data_ptr(), disp.data_ptr(), gout.data_ptr(),
+          gr.data_ptr() if want_right else None, gd.data_ptr() if want_disp else None, B, C, H, W)
+    return gr, gd
+
+
+_UPS_BWD_FLOATS = {}
+
+
+def dynamic_upsample3_backward(logits, disp, gout, want_disp=True):
+    """-> (g_logits [B,81,h,w], g_disp [B,h,w] or None).  The workspace comes from torch.empty, its size from the library's
+    query, cached per shape."""
+    B, h, w = _chk("disp", disp).shape
+    _chk("logits", logits, (B, 81, h, w))
+    _chk("gout", gout, (B, 3 * h, 3 * w))
+    gl = torch.empty_like(logits)
+    gd = ws = None
+    nws = 0
+    if want_disp:
+        nws = _UPS_BWD_FLOATS.get((B, h, w))
+        if nws is None:
+            nws = _UPS_BWD_FLOATS[(B, h, w)] = int(size("dynamic_upsample3_backward_workspace_floats", B, h, w))
+        if nws == 0:
+            raise _lib.DecnetHipError("decnet_dynamic_upsample3_backward does not cover B %d, %d x %d" % (B, h, w))
+        gd = torch.empty_like(disp)
+        ws = torch.empty(nws, dtype=_F32, device=disp.device)         # torch allocations are 16-byte aligned
+    _call("decnet_dynamic_upsample3_backward", logits, logits.data_ptr(), disp.data_ptr(), gout.data_ptr(), gl.data_ptr(),
+          gd.data_ptr() if want_disp else None, ws.data_ptr() if want_disp else None, nws, B, h, w)
+    return gl, gd
+
+
+def fold3(g, out=None):
+    """Inverse of unfold3_cat's feature part: g [B,9C+1,h,w] -> [B,C,3h,3w] (channel 0 is not read)."""
+    B, K, h, w = _chk("g", g).shape
+    if K < 10 or (K - 1) % 9:
+        raise ValueError("g has %d channels, not 9 C + 1" % K)
+    C = (K - 1) // 9
+    return _run("decnet_fold3", (g,), out, (B, C, 3 * h, 3 * w), B, C, h, w)
+
+
+def sigmoid_blend(o, a, b, out=None):
+    """a * (1 - sigmoid(o)) + sigmoid(o) * b over planes of one shape: conv2d_cat_epilogue's epilogue 1 on its own."""
+    _chk("b", b, _chk("a", a, _chk("o", o).shape).shape)
+    return _run("decnet_sigmoid_blend", (o, a, b), out, o.shape, o.numel())
+
+
+def sigmoid_blend_backward(o, a, b, gout, want_a=True, want_b=True):
+    """-> (g_o, g_a or None, g_b or None)."""
+    for n, t in (("a", a), ("b", b), ("gout", gout)):
+        _chk(n, t, _chk("o", o).shape)
+    go = torch.empty_like(o)
+    ga = torch.empty_like(o) if want_a else None
+    gb = torch.empty_like(o) if want_b else None
+    _call("decnet_sigmoid_blend_backward", o, o.data_ptr(), a.data_ptr(), b.data_ptr(), gout.data_ptr(), go.data_ptr(),
+          ga.data_ptr() if want_a else None, gb.data_ptr() if want_b else None, o.numel())
+    return go, ga, gb
+
+
 def detail_mask_params(flat):
     """The 92 folded host values of GenerateSparseMask.conv as the entry takes them: w3x3, scale3, shift3, w1x1, s1, b1."""
     arr = lambda v: (ctypes.c_float * len(v))(*v)  # noqa: E731

@@ -428,6 +428,44 @@ int decnet_detail_mask(const float *cur3, const float *pre3, const float *w3x3, 
  * fea [B,C,3h,3w], disp [B,h,w] -> out [B,9C+1,h,w], out[b,0] = disp, out[b,1+9c+3i+j,y,x] = fea[b,c,3y+i,3x+j]. */
 int decnet_unfold3_cat(const float *fea, const float *disp, float *out, int B, int C, int h, int w,
                        void *stream);
+/* ---- the full-resolution tail under hip_grad() (csrc/tail_grad.hip) -------------------------------------------------
+ * Backward of decnet_warp_disparity, decnet_dynamic_upsample3 and decnet_unfold3_cat, and SoftAttention's sigmoid + blend
+ * with its backward.  Common to all: fp32 planes at any float alignment; every output element is written; every sum is a
+ * gather in a fixed order (no atomics: the same bits on every run); no allocation, no synchronisation (capturable);
+ * nothing is launched on any refusal.
+ *
+ * decnet_warp_disparity_backward: gout [B,C,H,W] -> g_right [B,C,H,W] and / or g_disp [B,H,W] (each may be NULL, not
+ * both).  The sampling position is the forward's fp32 operation sequence, so the cell floor(ix), floor(iy) is the forward's.
+ *   g_disp[b,y,x]     = -W/(W-1) sum_c gout[b,c,y,x] ((v_ne - v_nw)(1 - t_y) + (v_se - v_sw) t_y), t_y = iy - floor(iy),
+ *                       taps outside the image zero, channels summed in rising order
+ *   g_right[b,c,y',x'] = sum_{(y,x)} w_y(y,y') w_x(y,x,x') gout[b,c,y,x]: the transpose of the forward, contributing rows y
+ *                       rising, then x rising
+ * H < 2 or W < 2: DECNET_ERR_BAD_SHAPE; the forward's grid limits, and for g_right W > 1819 (the row's positions and
+ * eight channels of gout are staged in 64 KiB of LDS): DECNET_ERR_UNSUPPORTED.  Disparities must be finite; ones that
+ * push every tap off the image give zero gradients. */
+int decnet_warp_disparity_backward(const float *right, const float *disp, const float *gout, float *g_right,
+                                   float *g_disp, int B, int C, int H, int W, void *stream);
+/* decnet_dynamic_upsample3_backward: gout [B,3h,3w] -> g_logits [B,81,h,w] and, unless NULL, g_disp [B,h,w].  With
+ * p = softmax_k(logits[9 s + k]) (the forward's max-subtracted expf), n_k the replicate-padded neighbours and
+ * m_s = sum_k p_k n_k:  g_logits[9 s + k] = 3 gout_s p_k (n_k - m_s);  g_disp[Y,X] = sum of q_k(y,x) = 3 sum_s gout_s p_{s,k}
+ * over every (y, x, k) whose clamped neighbour is (Y,X), in the order y, x, k rising.
+ *   workspace   q [B,9,h,w]: decnet_dynamic_upsample3_backward_workspace_floats(B, h, w) floats (0: shape not covered),
+ *               16-byte aligned; read only with g_disp.  With g_disp given: NULL is DECNET_ERR_NULL_POINTER, fewer floats
+ *               than the query DECNET_ERR_BAD_SHAPE, a misaligned one DECNET_ERR_MISALIGNED.
+ * h or B > 65535: DECNET_ERR_UNSUPPORTED. */
+size_t decnet_dynamic_upsample3_backward_workspace_floats(int B, int h, int w);
+int decnet_dynamic_upsample3_backward(const float *logits, const float *disp, const float *gout, float *g_logits,
+                                      float *g_disp, float *workspace, size_t workspace_floats, int B, int h, int w,
+                                      void *stream);
+/* Inverse of decnet_unfold3_cat's feature part: g [B,9C+1,h,w] -> g_fea [B,C,3h,3w], g_fea[b,c,3y+i,3x+j] =
+ * g[b,1+9c+3i+j,y,x] (channel 0, the disparity plane, is not read).  Limits as decnet_unfold3_cat. */
+int decnet_fold3(const float *g, float *g_fea, int B, int C, int h, int w, void *stream);
+/* SoftAttention's tail over n floats: s = 1 / (1 + expf(-o)), out = a (1 - s) + s b -- the statement sequence of
+ * decnet_conv2d_cat_epilogue's epilogue 1, so the same bits.  Backward: g_o = gout (b - a) s (1 - s), g_a = gout (1 - s),
+ * g_b = gout s (g_a, g_b: each may be NULL), s recomputed from o. */
+int decnet_sigmoid_blend(const float *o, const float *a, const float *b, float *out, size_t n, void *stream);
+int decnet_sigmoid_blend_backward(const float *o, const float *a, const float *b, const float *gout, float *g_o,
+                                  float *g_a, float *g_b, size_t n, void *stream);
 /* Space-to-depth in front of the stride-3 convolutions of FeatExtNetChannelPlus (Conv2d k 3, stride 3, padding 1,
  * submodule.py:270-300): x [B,C,H,W] -> out [B,9C,Ho,Wo], Ho = (H-1)/3+1, Wo = (W-1)/3+1,
  * out[b,c*9+ky*3+kx,yo,xo] = x[b,c,3yo-1+ky,3xo-1+kx] (0 outside); the convolution is then the 1 x 1 convolution with the
