@@ -1,45 +1,10 @@
 // decnet_amd/csrc/capi.hip -- extern "C" entry points for SpaMat / SpaVar (include/decnet_hip.h).
-#include "common.h"
-
-// kernels in spamat_rowtile.hip
-int decnet_rowtile_forward(int mode, const float *ref, const float *tar, const float *rmask,
-                           const float *tmask, const float *disparity, float *out, float *var_out,
-                           float *sum_sim, float *max_cost, int B, int C, int H, int W, int max_disp,
-                           hipStream_t stream);
-int decnet_rowtile_backward(int var, const float *ref, const float *tar, const float *rmask,
-                            const float *tmask, const float *disparity, const float *out,
-                            const float *sum_sim, const float *max_cost, const float *grad_out,
-                            float *grad_ref, float *grad_tar, float *grad_disp, int B, int C, int H,
-                            int W, int max_disp, hipStream_t stream);
-int decnet_check_spamat_args(const void *const *ptrs, int n, int B, int C, int H, int W,
-                             int max_disp);
-// kernels in spamat_mfma.hip (banded cost tiles on the matrix cores)
-int decnet_mfma_forward(int mode, const float *ref, const float *tar, const float *rmask,
-                        const float *tmask, const float *disparity, float *out, float *var_out,
-                        float *sum_sim, float *max_cost, int B, int C, int H, int W, int max_disp,
-                        int allow_compact, int mbits, hipStream_t stream);
-
-// kernels in spamat_bwd_mfma.hip
-int decnet_mfma_backward(int var, const float *ref, const float *tar, const float *rmask,
-                         const float *tmask, const float *disparity, const float *out,
-                         const float *sum_sim, const float *max_cost, const float *grad_out,
-                         float *grad_ref, float *grad_tar, float *grad_disp, int B, int C, int H,
-                         int W, int max_disp, hipStream_t stream);
-
-// spamat_wide.hip: disparity ranges wider than 18 tiles (max_disp > 273) as several band-kernel calls + per-pixel merges.
-// ws: the caller's workspace of decnet_wide_workspace_floats floats (the `_ws` entries), or nullptr (the legacy entries: the
-// sweep allocates its scratch, and is UNSUPPORTED while the stream is being captured)
-int decnet_wide_forward(int mode, const float *ref, const float *tar, const float *rmask, const float *tmask,
-                        const float *disparity, float *out, float *var_out, float *sum_sim, float *max_cost, int B, int C,
-                        int H, int W, int D, int allow_compact, int mbits, float *ws, hipStream_t stream);
-int decnet_wide_backward(int var, const float *ref, const float *tar, const float *rmask, const float *tmask,
-                         const float *disparity, const float *out, const float *sum_sim, const float *max_cost,
-                         const float *grad_out, float *grad_ref, float *grad_tar, float *grad_disp, int B, int C, int H,
-                         int W, int D, float *ws, hipStream_t stream);
-size_t decnet_wide_workspace_floats(int B, int C, int H, int W, int D, int which);
+#include "spamat_host.h"
 
 #include <stdlib.h>
 #include <string.h>
+
+#include <initializer_list>
 
 static int spamat_pinned() {       // DECNET_SPAMAT_KERNEL, read once
     static const int pinned = [] {
@@ -107,50 +72,6 @@ static int check_finite(const float *ref, const float *tar, int B, int C, int H,
     return h ? DECNET_ERR_NONFINITE : 0;
 }
 
-// Backward dispatch: matrix-core kernels, row-tile kernels for what they do not cover.  ws: the wide sweep's scratch from
-// the caller (the `_ws` entries, checked by check_workspace), or nullptr (the legacy entries).
-static int backward_dispatch(int var, const float *ref, const float *tar, const float *rmask,
-                             const float *tmask, const float *disparity, const float *out,
-                             const float *sum_sim, const float *max_cost, const float *grad_out,
-                             float *grad_ref, float *grad_tar, float *grad_disp, int B, int C, int H,
-                             int W, int max_disp, float *ws, hipStream_t stream) {
-    const int pinned = spamat_pinned();
-    if (pinned != 1) {
-        int rc = decnet_mfma_backward(var, ref, tar, rmask, tmask, disparity, out, sum_sim, max_cost,
-                                      grad_out, grad_ref, grad_tar, grad_disp, B, C, H, W, max_disp,
-                                      stream);
-        if (rc == DECNET_ERR_UNSUPPORTED && max_disp > 272)       // wider than 18 tiles: the same kernels band by band
-            rc = decnet_wide_backward(var, ref, tar, rmask, tmask, disparity, out, sum_sim, max_cost, grad_out, grad_ref,
-                                      grad_tar, grad_disp, B, C, H, W, max_disp, ws, stream);
-        if (rc != DECNET_ERR_UNSUPPORTED || pinned >= 2) return rc;
-    }
-    return decnet_rowtile_backward(var, ref, tar, rmask, tmask, disparity, out, sum_sim, max_cost,
-                                   grad_out, grad_ref, grad_tar, grad_disp, B, C, H, W, max_disp,
-                                   stream);
-}
-
-// Forward dispatch: the MFMA band kernel; the row-tile kernel covers what it cannot
-// (band wider than 18 tiles, LDS overflow).  DECNET_SPAMAT_KERNEL=rowtile|mfma|mfma_dense pins
-// one variant (read once; used by the A/B benchmarks and the parity tests of the variants);
-// mfma_dense = MFMA kernel with the sparse-row compaction path switched off.
-static int forward_dispatch(int mode, const float *ref, const float *tar, const float *rmask,
-                            const float *tmask, const float *disparity, float *out, float *var_out,
-                            float *sum_sim, float *max_cost, int B, int C, int H, int W,
-                            int max_disp, float *ws, hipStream_t stream) {
-    const int pinned = spamat_pinned();
-    if (int rc = check_finite(ref, tar, B, C, H, W, stream)) return rc;
-    if (pinned != 1) {
-        int rc = decnet_mfma_forward(mode, ref, tar, rmask, tmask, disparity, out, var_out, sum_sim,
-                                     max_cost, B, C, H, W, max_disp, pinned != 3, 0, stream);
-        if (rc == DECNET_ERR_UNSUPPORTED && max_disp > 272)       // wider than 18 tiles: the same kernels band by band
-            rc = decnet_wide_forward(mode, ref, tar, rmask, tmask, disparity, out, var_out, sum_sim, max_cost, B, C, H, W,
-                                     max_disp, pinned != 3, 0, ws, stream);
-        if (rc != DECNET_ERR_UNSUPPORTED || pinned >= 2) return rc;
-    }
-    return decnet_rowtile_forward(mode, ref, tar, rmask, tmask, disparity, out, var_out, sum_sim,
-                                  max_cost, B, C, H, W, max_disp, stream);
-}
-
 // ---- the caller-workspace (`_ws`) entries ------------------------------------------------------------------------------
 // workspace floats of entry `which` (include/decnet_hip.h); 0 for bad shapes and wherever one band takes the call
 static size_t workspace_floats(int B, int C, int H, int W, int max_disp, int which) {
@@ -177,129 +98,138 @@ struct Workspace {
     }
 };
 
-static int spamat_forward(const float *ref, const float *tar, const float *ref_mask, const float *tar_mask, float *output,
-                          float *sum_similarities, float *max_cost, int B, int C, int H, int W, int max_disp, Workspace ws,
-                          void *stream) {
-    const void *p[] = {ref, tar, ref_mask, tar_mask, output, sum_similarities, max_cost};
-    int rc = decnet_check_spamat_args(p, 7, B, C, H, W, max_disp);
-    if (rc) return rc;
-    if ((rc = ws.check(B, C, H, W, max_disp, 0))) return rc;
-    return forward_dispatch(0, ref, tar, ref_mask, tar_mask, nullptr, output, nullptr,
-                                  sum_similarities, max_cost, B, C, H, W, max_disp, ws.p,
-                                  (hipStream_t)stream);
+// ---- one call path per direction ---------------------------------------------------------------------------------------
+// `which` is the entry as decnet_spamat_workspace_floats numbers them: 0 spamat_forward, 1 spavar_forward,
+// 2 spamatvar_forward, 3 spamatvar_forward_bits, 4 spamat_backward, 5 spavar_backward; it says which pointers of the record
+// the entry has and which workspace it needs.  Order of rejection: null tensor pointer, bad shape, workspace (null / short /
+// misaligned), check_finite, launch.
+static int check_args(std::initializer_list<const void *> ptrs, int B, int C, int H, int W, int max_disp) {
+    for (const void *p : ptrs)
+        if (!p) return DECNET_ERR_NULL_POINTER;
+    if (B < 1 || C < 1 || H < 1 || W < 1 || max_disp < 1) return DECNET_ERR_BAD_SHAPE;
+    if ((double)B * C * H * W >= 2147483648.0) return DECNET_ERR_BAD_SHAPE;
+    return DECNET_OK;
 }
 
-static int spavar_forward(const float *ref, const float *tar, const float *ref_mask, const float *tar_mask,
-                          const float *disparity, float *output, float *sum_similarities, float *max_cost, int B, int C,
-                          int H, int W, int max_disp, Workspace ws, void *stream) {
-    const void *p[] = {ref, tar, ref_mask, tar_mask, disparity, output, sum_similarities, max_cost};
-    int rc = decnet_check_spamat_args(p, 8, B, C, H, W, max_disp);
+// Forward dispatch: the MFMA band kernel; the row-tile kernel covers what it cannot
+// (band wider than 18 tiles, LDS overflow).  DECNET_SPAMAT_KERNEL=rowtile|mfma|mfma_dense pins
+// one variant (read once; used by the A/B benchmarks and the parity tests of the variants);
+// mfma_dense = MFMA kernel with the sparse-row compaction path switched off.
+// The bit-mask entry (a.mbits) has the matrix-core kernels only (the row-tile fallback reads float planes); above max_disp
+// 273 (18 tiles) band by band with the masks unpacked into scratch planes (spamat_wide.hip; the legacy entry, whose sweep
+// allocates, is UNSUPPORTED there while the stream is being captured; the `_ws` entry is not).
+// DECNET_SPAMAT_KERNEL=rowtile pins a kernel that entry does not have -> UNSUPPORTED, the caller falls back to the
+// float-mask entry (decnet_amd.model does)
+static int run_forward(SpaFwd a, int which, Workspace ws) {
+    // the one or two outputs and the disparity input differ by entry: out (0), disparity + var_out (1), out + var_out (2, 3)
+    int rc = check_args({a.ref, a.tar, a.rmask, a.tmask, which == 1 ? a.disparity : a.out,
+                         which ? a.var_out : a.out, a.sum_sim, a.max_cost}, a.B, a.C, a.H, a.W, a.D);
     if (rc) return rc;
-    if ((rc = ws.check(B, C, H, W, max_disp, 1))) return rc;
-    return forward_dispatch(1, ref, tar, ref_mask, tar_mask, disparity, nullptr, output,
-                                  sum_similarities, max_cost, B, C, H, W, max_disp, ws.p,
-                                  (hipStream_t)stream);
+    if ((rc = ws.check(a.B, a.C, a.H, a.W, a.D, which))) return rc;
+    const int pinned = spamat_pinned();
+    if (a.mbits && pinned == 1) return DECNET_ERR_UNSUPPORTED;
+    if ((rc = check_finite(a.ref, a.tar, a.B, a.C, a.H, a.W, a.stream))) return rc;
+    if (pinned == 3) a.allow_compact = 0;
+    if (pinned != 1) {
+        rc = decnet_mfma_forward(a);
+        if (rc == DECNET_ERR_UNSUPPORTED && a.D > SPAMAT_BAND_DISP)   // wider than 18 tiles: the same kernels band by band
+            rc = decnet_wide_forward(a, ws.p);
+        if (rc != DECNET_ERR_UNSUPPORTED || pinned >= 2 || a.mbits) return rc;
+    }
+    return decnet_rowtile_forward(a);
 }
 
-static int spamatvar_forward(const float *ref, const float *tar, const float *ref_mask, const float *tar_mask,
-                             float *output, float *variance, float *sum_similarities, float *max_cost, int B, int C, int H,
-                             int W, int max_disp, Workspace ws, void *stream) {
-    const void *p[] = {ref, tar, ref_mask, tar_mask, output, variance, sum_similarities, max_cost};
-    int rc = decnet_check_spamat_args(p, 8, B, C, H, W, max_disp);
+// Backward dispatch: matrix-core kernels, row-tile kernels for what they do not cover.  ws.p: the wide sweep's scratch from
+// the caller (the `_ws` entries, checked by ws.check), or nullptr (the legacy entries).
+static int run_backward(const SpaBwd &a, int which, Workspace ws) {
+    // SpaVar (5) also has the disparity input and its gradient
+    int rc = check_args({a.ref, a.tar, a.rmask, a.tmask, a.out, a.sum_sim, a.max_cost, a.grad_out, a.grad_ref, a.grad_tar,
+                         which == 5 ? a.disparity : a.ref, which == 5 ? a.grad_disp : a.grad_ref}, a.B, a.C, a.H, a.W, a.D);
     if (rc) return rc;
-    if ((rc = ws.check(B, C, H, W, max_disp, 2))) return rc;
-    return forward_dispatch(2, ref, tar, ref_mask, tar_mask, nullptr, output, variance,
-                                  sum_similarities, max_cost, B, C, H, W, max_disp, ws.p,
-                                  (hipStream_t)stream);
+    if ((rc = ws.check(a.B, a.C, a.H, a.W, a.D, which))) return rc;
+    const int pinned = spamat_pinned();
+    if (pinned != 1) {
+        rc = decnet_mfma_backward(a);
+        if (rc == DECNET_ERR_UNSUPPORTED && a.D > SPAMAT_BAND_DISP)   // wider than 18 tiles: the same kernels band by band
+            rc = decnet_wide_backward(a, ws.p);
+        if (rc != DECNET_ERR_UNSUPPORTED || pinned >= 2) return rc;
+    }
+    return decnet_rowtile_backward(a);
 }
 
-static int spamatvar_forward_bits(const float *ref, const float *tar, const unsigned long long *ref_bits,
-                                  const unsigned long long *tar_bits, float *output, float *variance,
-                                  float *sum_similarities, float *max_cost, int B, int C, int H, int W, int max_disp,
-                                  Workspace ws, void *stream) {
-    const void *p[] = {ref, tar, ref_bits, tar_bits, output, variance, sum_similarities, max_cost};
-    int rc = decnet_check_spamat_args(p, 8, B, C, H, W, max_disp);
-    if (rc) return rc;
-    if ((rc = ws.check(B, C, H, W, max_disp, 3))) return rc;
-    // the matrix-core kernels only (the row-tile fallback reads float planes); above max_disp 273 (18 tiles) band by
-    // band with the masks unpacked into scratch planes (spamat_wide.hip; the legacy entry, whose sweep allocates, is
-    // UNSUPPORTED there while the stream is being captured; the `_ws` entry is not).
-    // DECNET_SPAMAT_KERNEL=rowtile pins a kernel this entry does not have -> UNSUPPORTED, the caller falls back to the
-    // float-mask entry (decnet_amd.model does)
-    if (spamat_pinned() == 1) return DECNET_ERR_UNSUPPORTED;
-    if (int rc2 = check_finite(ref, tar, B, C, H, W, (hipStream_t)stream)) return rc2;
-    rc = decnet_mfma_forward(2, ref, tar, reinterpret_cast<const float *>(ref_bits),
-                             reinterpret_cast<const float *>(tar_bits), nullptr, output, variance,
-                             sum_similarities, max_cost, B, C, H, W, max_disp, spamat_pinned() != 3, 1,
-                             (hipStream_t)stream);
-    if (rc == DECNET_ERR_UNSUPPORTED && max_disp > 272)
-        rc = decnet_wide_forward(2, ref, tar, reinterpret_cast<const float *>(ref_bits),
-                                 reinterpret_cast<const float *>(tar_bits), nullptr, output, variance, sum_similarities,
-                                 max_cost, B, C, H, W, max_disp, spamat_pinned() != 3, 1, ws.p, (hipStream_t)stream);
-    return rc;
-}
-
-static int spamat_backward(const float *ref, const float *tar, const float *ref_mask, const float *tar_mask,
-                           const float *output, const float *sum_similarities, const float *max_cost,
-                           const float *grad_output, float *grad_ref, float *grad_tar, int B, int C, int H, int W,
-                           int max_disp, Workspace ws, void *stream) {
-    const void *p[] = {ref, tar, ref_mask, tar_mask, output, sum_similarities, max_cost,
-                       grad_output, grad_ref, grad_tar};
-    int rc = decnet_check_spamat_args(p, 10, B, C, H, W, max_disp);
-    if (rc) return rc;
-    if ((rc = ws.check(B, C, H, W, max_disp, 4))) return rc;
-    return backward_dispatch(0, ref, tar, ref_mask, tar_mask, nullptr, output,
-                                   sum_similarities, max_cost, grad_output, grad_ref, grad_tar,
-                                   nullptr, B, C, H, W, max_disp, ws.p, (hipStream_t)stream);
-}
-
-static int spavar_backward(const float *ref, const float *tar, const float *ref_mask, const float *tar_mask,
-                           const float *disparity, const float *output, const float *sum_similarities,
-                           const float *max_cost, const float *grad_output, float *grad_ref, float *grad_tar,
-                           float *grad_disparity, int B, int C, int H, int W, int max_disp, Workspace ws, void *stream) {
-    const void *p[] = {ref, tar, ref_mask, tar_mask, disparity, output, sum_similarities, max_cost,
-                       grad_output, grad_ref, grad_tar, grad_disparity};
-    int rc = decnet_check_spamat_args(p, 12, B, C, H, W, max_disp);
-    if (rc) return rc;
-    if ((rc = ws.check(B, C, H, W, max_disp, 5))) return rc;
-    return backward_dispatch(1, ref, tar, ref_mask, tar_mask, disparity, output,
-                                   sum_similarities, max_cost, grad_output, grad_ref, grad_tar,
-                                   grad_disparity, B, C, H, W, max_disp, ws.p, (hipStream_t)stream);
-}
+// the bit-packed masks of decnet_spamatvar_forward_bits travel in the record's float-mask fields (SpaFwd::mbits)
+static const float *mask_bits(const unsigned long long *bits) { return reinterpret_cast<const float *>(bits); }
 
 extern "C" {
 
 const char *decnet_version(void) { return "decnet_hip 0.1.0 gfx950"; }
 
+size_t decnet_spamat_workspace_floats(int B, int C, int H, int W, int max_disp, int which) {
+    return workspace_floats(B, C, H, W, max_disp, which);
+}
+
+// Each entry fills the record -- {mode / var, inputs, outputs, dims, (allow_compact, mbits,) stream}, nullptr for what the
+// entry does not have -- and names itself (`which`) and its workspace.
+
 int decnet_spamat_forward(const float *ref, const float *tar, const float *ref_mask,
                           const float *tar_mask, float *output, float *sum_similarities,
                           float *max_cost, int B, int C, int H, int W, int max_disp, void *stream) {
-    return spamat_forward(ref, tar, ref_mask, tar_mask, output, sum_similarities, max_cost, B, C, H, W, max_disp,
-                          Workspace::legacy(), stream);
+    return run_forward({MODE_MAT, ref, tar, ref_mask, tar_mask, nullptr, output, nullptr, sum_similarities, max_cost,
+                        B, C, H, W, max_disp, 1, 0, (hipStream_t)stream}, 0, Workspace::legacy());
+}
+
+int decnet_spamat_forward_ws(const float *ref, const float *tar, const float *ref_mask, const float *tar_mask,
+                             float *output, float *sum_similarities, float *max_cost, int B, int C, int H, int W,
+                             int max_disp, float *workspace, size_t workspace_floats, void *stream) {
+    return run_forward({MODE_MAT, ref, tar, ref_mask, tar_mask, nullptr, output, nullptr, sum_similarities, max_cost,
+                        B, C, H, W, max_disp, 1, 0, (hipStream_t)stream}, 0, Workspace{workspace, workspace_floats, true});
 }
 
 int decnet_spavar_forward(const float *ref, const float *tar, const float *ref_mask,
                           const float *tar_mask, const float *disparity, float *output,
                           float *sum_similarities, float *max_cost, int B, int C, int H, int W,
                           int max_disp, void *stream) {
-    return spavar_forward(ref, tar, ref_mask, tar_mask, disparity, output, sum_similarities, max_cost, B, C, H, W,
-                          max_disp, Workspace::legacy(), stream);
+    return run_forward({MODE_VAR, ref, tar, ref_mask, tar_mask, disparity, nullptr, output, sum_similarities, max_cost,
+                        B, C, H, W, max_disp, 1, 0, (hipStream_t)stream}, 1, Workspace::legacy());
+}
+
+int decnet_spavar_forward_ws(const float *ref, const float *tar, const float *ref_mask, const float *tar_mask,
+                             const float *disparity, float *output, float *sum_similarities, float *max_cost, int B,
+                             int C, int H, int W, int max_disp, float *workspace, size_t workspace_floats, void *stream) {
+    return run_forward({MODE_VAR, ref, tar, ref_mask, tar_mask, disparity, nullptr, output, sum_similarities, max_cost,
+                        B, C, H, W, max_disp, 1, 0, (hipStream_t)stream}, 1, Workspace{workspace, workspace_floats, true});
 }
 
 int decnet_spamatvar_forward(const float *ref, const float *tar, const float *ref_mask,
                              const float *tar_mask, float *output, float *variance,
                              float *sum_similarities, float *max_cost, int B, int C, int H, int W,
                              int max_disp, void *stream) {
-    return spamatvar_forward(ref, tar, ref_mask, tar_mask, output, variance, sum_similarities, max_cost, B, C, H, W,
-                             max_disp, Workspace::legacy(), stream);
+    return run_forward({MODE_FUSED, ref, tar, ref_mask, tar_mask, nullptr, output, variance, sum_similarities, max_cost,
+                        B, C, H, W, max_disp, 1, 0, (hipStream_t)stream}, 2, Workspace::legacy());
+}
+
+int decnet_spamatvar_forward_ws(const float *ref, const float *tar, const float *ref_mask, const float *tar_mask,
+                                float *output, float *variance, float *sum_similarities, float *max_cost, int B, int C,
+                                int H, int W, int max_disp, float *workspace, size_t workspace_floats, void *stream) {
+    return run_forward({MODE_FUSED, ref, tar, ref_mask, tar_mask, nullptr, output, variance, sum_similarities, max_cost,
+                        B, C, H, W, max_disp, 1, 0, (hipStream_t)stream}, 2, Workspace{workspace, workspace_floats, true});
 }
 
 int decnet_spamatvar_forward_bits(const float *ref, const float *tar, const unsigned long long *ref_bits,
                                   const unsigned long long *tar_bits, float *output, float *variance,
                                   float *sum_similarities, float *max_cost, int B, int C, int H, int W,
                                   int max_disp, void *stream) {
-    return spamatvar_forward_bits(ref, tar, ref_bits, tar_bits, output, variance, sum_similarities, max_cost, B, C, H, W,
-                                  max_disp, Workspace::legacy(), stream);
+    return run_forward({MODE_FUSED, ref, tar, mask_bits(ref_bits), mask_bits(tar_bits), nullptr, output, variance,
+                        sum_similarities, max_cost, B, C, H, W, max_disp, 1, 1, (hipStream_t)stream}, 3, Workspace::legacy());
+}
+
+int decnet_spamatvar_forward_bits_ws(const float *ref, const float *tar, const unsigned long long *ref_bits,
+                                     const unsigned long long *tar_bits, float *output, float *variance,
+                                     float *sum_similarities, float *max_cost, int B, int C, int H, int W, int max_disp,
+                                     float *workspace, size_t workspace_floats, void *stream) {
+    return run_forward({MODE_FUSED, ref, tar, mask_bits(ref_bits), mask_bits(tar_bits), nullptr, output, variance,
+                        sum_similarities, max_cost, B, C, H, W, max_disp, 1, 1, (hipStream_t)stream}, 3,
+                       Workspace{workspace, workspace_floats, true});
 }
 
 int decnet_spamat_backward(const float *ref, const float *tar, const float *ref_mask,
@@ -307,8 +237,17 @@ int decnet_spamat_backward(const float *ref, const float *tar, const float *ref_
                            const float *sum_similarities, const float *max_cost,
                            const float *grad_output, float *grad_ref, float *grad_tar, int B, int C,
                            int H, int W, int max_disp, void *stream) {
-    return spamat_backward(ref, tar, ref_mask, tar_mask, output, sum_similarities, max_cost, grad_output, grad_ref,
-                           grad_tar, B, C, H, W, max_disp, Workspace::legacy(), stream);
+    return run_backward({0, ref, tar, ref_mask, tar_mask, nullptr, output, sum_similarities, max_cost, grad_output,
+                         grad_ref, grad_tar, nullptr, B, C, H, W, max_disp, (hipStream_t)stream}, 4, Workspace::legacy());
+}
+
+int decnet_spamat_backward_ws(const float *ref, const float *tar, const float *ref_mask, const float *tar_mask,
+                              const float *output, const float *sum_similarities, const float *max_cost,
+                              const float *grad_output, float *grad_ref, float *grad_tar, int B, int C, int H, int W,
+                              int max_disp, float *workspace, size_t workspace_floats, void *stream) {
+    return run_backward({0, ref, tar, ref_mask, tar_mask, nullptr, output, sum_similarities, max_cost, grad_output,
+                         grad_ref, grad_tar, nullptr, B, C, H, W, max_disp, (hipStream_t)stream}, 4,
+                        Workspace{workspace, workspace_floats, true});
 }
 
 int decnet_spavar_backward(const float *ref, const float *tar, const float *ref_mask,
@@ -317,49 +256,9 @@ int decnet_spavar_backward(const float *ref, const float *tar, const float *ref_
                            const float *grad_output, float *grad_ref, float *grad_tar,
                            float *grad_disparity, int B, int C, int H, int W, int max_disp,
                            void *stream) {
-    return spavar_backward(ref, tar, ref_mask, tar_mask, disparity, output, sum_similarities, max_cost, grad_output,
-                           grad_ref, grad_tar, grad_disparity, B, C, H, W, max_disp, Workspace::legacy(), stream);
-}
-
-size_t decnet_spamat_workspace_floats(int B, int C, int H, int W, int max_disp, int which) {
-    return workspace_floats(B, C, H, W, max_disp, which);
-}
-
-int decnet_spamat_forward_ws(const float *ref, const float *tar, const float *ref_mask, const float *tar_mask,
-                             float *output, float *sum_similarities, float *max_cost, int B, int C, int H, int W,
-                             int max_disp, float *workspace, size_t workspace_floats, void *stream) {
-    return spamat_forward(ref, tar, ref_mask, tar_mask, output, sum_similarities, max_cost, B, C, H, W, max_disp,
-                          Workspace{workspace, workspace_floats, true}, stream);
-}
-
-int decnet_spavar_forward_ws(const float *ref, const float *tar, const float *ref_mask, const float *tar_mask,
-                             const float *disparity, float *output, float *sum_similarities, float *max_cost, int B,
-                             int C, int H, int W, int max_disp, float *workspace, size_t workspace_floats, void *stream) {
-    return spavar_forward(ref, tar, ref_mask, tar_mask, disparity, output, sum_similarities, max_cost, B, C, H, W,
-                          max_disp, Workspace{workspace, workspace_floats, true}, stream);
-}
-
-int decnet_spamatvar_forward_ws(const float *ref, const float *tar, const float *ref_mask, const float *tar_mask,
-                                float *output, float *variance, float *sum_similarities, float *max_cost, int B, int C,
-                                int H, int W, int max_disp, float *workspace, size_t workspace_floats, void *stream) {
-    return spamatvar_forward(ref, tar, ref_mask, tar_mask, output, variance, sum_similarities, max_cost, B, C, H, W,
-                             max_disp, Workspace{workspace, workspace_floats, true}, stream);
-}
-
-int decnet_spamatvar_forward_bits_ws(const float *ref, const float *tar, const unsigned long long *ref_bits,
-                                     const unsigned long long *tar_bits, float *output, float *variance,
-                                     float *sum_similarities, float *max_cost, int B, int C, int H, int W, int max_disp,
-                                     float *workspace, size_t workspace_floats, void *stream) {
-    return spamatvar_forward_bits(ref, tar, ref_bits, tar_bits, output, variance, sum_similarities, max_cost, B, C, H, W,
-                                  max_disp, Workspace{workspace, workspace_floats, true}, stream);
-}
-
-int decnet_spamat_backward_ws(const float *ref, const float *tar, const float *ref_mask, const float *tar_mask,
-                              const float *output, const float *sum_similarities, const float *max_cost,
-                              const float *grad_output, float *grad_ref, float *grad_tar, int B, int C, int H, int W,
-                              int max_disp, float *workspace, size_t workspace_floats, void *stream) {
-    return spamat_backward(ref, tar, ref_mask, tar_mask, output, sum_similarities, max_cost, grad_output, grad_ref,
-                           grad_tar, B, C, H, W, max_disp, Workspace{workspace, workspace_floats, true}, stream);
+    return run_backward({1, ref, tar, ref_mask, tar_mask, disparity, output, sum_similarities, max_cost, grad_output,
+                         grad_ref, grad_tar, grad_disparity, B, C, H, W, max_disp, (hipStream_t)stream}, 5,
+                        Workspace::legacy());
 }
 
 int decnet_spavar_backward_ws(const float *ref, const float *tar, const float *ref_mask, const float *tar_mask,
@@ -367,9 +266,9 @@ int decnet_spavar_backward_ws(const float *ref, const float *tar, const float *r
                               const float *max_cost, const float *grad_output, float *grad_ref, float *grad_tar,
                               float *grad_disparity, int B, int C, int H, int W, int max_disp, float *workspace,
                               size_t workspace_floats, void *stream) {
-    return spavar_backward(ref, tar, ref_mask, tar_mask, disparity, output, sum_similarities, max_cost, grad_output,
-                           grad_ref, grad_tar, grad_disparity, B, C, H, W, max_disp,
-                           Workspace{workspace, workspace_floats, true}, stream);
+    return run_backward({1, ref, tar, ref_mask, tar_mask, disparity, output, sum_similarities, max_cost, grad_output,
+                         grad_ref, grad_tar, grad_disparity, B, C, H, W, max_disp, (hipStream_t)stream}, 5,
+                        Workspace{workspace, workspace_floats, true});
 }
 
 }  // extern "C"

@@ -17,6 +17,19 @@ static inline int decnet_launch_status() {
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
 #ifdef __HIPCC__
+// One kernel launch with lds_bytes of dynamic LDS; more than 64 KiB needs the kernel's limit raised first.  Returns
+// DECNET_OK or the first hipError_t (nothing is launched when raising the limit fails).
+template <typename K, typename... Args>
+static inline int decnet_launch(K kernel, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream, Args... args) {
+    if (lds_bytes > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        if (e != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, args...);
+    return decnet_launch_status();
+}
+
+
 // The cost of one (left, right) feature pair, GetCostVolume.cost_computation_* (submodule.py:511-530), with the
 // reference's fp32 operation sequence (no contraction): CF = DECNET_COST_COR l * r (:521); DECNET_COST_SSD
 // (l^2 + r^2) / 2 - ((l + r) / 2)^2 as torch evaluates :527-529 (pow_(2) is x * x, div_(2) is exact);

@@ -22,9 +22,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <type_traits>
-
-#include "common.h"
+#include "spamat_host.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -445,25 +443,17 @@ int side_xt(int cq, int W) {
 }
 
 template <int NT, bool VAR, int KQ>
-int launch_sides(const float *ref, const float *tar, const float *rmask, const float *tmask,
-                 const float *disparity, const float *out, const float *sum_sim, const float *max_cost,
-                 const float *grad_out, float *grad_ref, float *grad_tar, float *grad_disp, int B, int C, int H,
-                 int W, int D, int XT0, int XT1, int marker, hipStream_t stream) {
+int launch_sides(const SpaBwd &a, int XT0, int XT1, int marker) {
+    const int W = a.W;
     const size_t lds0 = (size_t)4 * make_blayout(4 * KQ, NT, XT0, 1, bwd_nown(0, VAR)).total;
     const size_t lds1 = (size_t)4 * make_blayout(4 * KQ, NT, XT1, VAR ? 5 : 4, bwd_nown(1, VAR)).total;
     const size_t lds = lds0 > lds1 ? lds0 : lds1;
     const int segs0 = ceil_div(ceil_div(W, 16), XT0), segs1 = ceil_div(ceil_div(W, 16), XT1);
-    const size_t n0 = (size_t)B * H * segs0, n1 = (size_t)B * H * segs1;
+    const size_t n0 = (size_t)a.B * a.H * segs0, n1 = (size_t)a.B * a.H * segs1;
     if (n0 + n1 >= 2147483648ull) return DECNET_ERR_UNSUPPORTED;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void *)spamat_bwd_mfma<NT, VAR, KQ>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    hipLaunchKernelGGL((spamat_bwd_mfma<NT, VAR, KQ>), dim3((unsigned)(n0 + n1)), dim3(THREADS), lds, stream, ref,
-                       tar, rmask, tmask, disparity, out, sum_sim, max_cost, grad_out, grad_ref, grad_tar, grad_disp, C,
-                       H, W, D, (int)n0, segs0, XT0, segs1, XT1, marker);
-    return decnet_launch_status();
+    return decnet_launch(spamat_bwd_mfma<NT, VAR, KQ>, dim3((unsigned)(n0 + n1)), dim3(THREADS), lds, a.stream, a.ref, a.tar,
+                         a.rmask, a.tmask, a.disparity, a.out, a.sum_sim, a.max_cost, a.grad_out, a.grad_ref, a.grad_tar,
+                         a.grad_disp, a.C, a.H, W, a.D, (int)n0, segs0, XT0, segs1, XT1, marker);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1172,20 +1162,16 @@ __global__ __launch_bounds__(64 * RB_NW, CB == 1 ? 4 : (CB == 3 && NT > 8) ? 2 :
 }
 
 template <int NT, int CB>
-int launch_row(const float *ref, const float *tar, const float *rmask, const float *tmask, const float *out,
-               const float *sum_sim, const float *max_cost, const float *grad_out, float *grad_ref, float *grad_tar,
-               int B, int C, int H, int W, int D, int marker, hipStream_t stream) {
-    if ((double)C * H * W >= 2147483648.0) return DECNET_ERR_UNSUPPORTED;        // 32-bit element offsets inside a sample
-    hipLaunchKernelGGL((spamat_bwd_rowb<NT, CB>), dim3((unsigned)((size_t)B * H)), dim3(64 * RB_NW), 0, stream, ref, tar, rmask,
-                       tmask, out, sum_sim, max_cost, grad_out, grad_ref, grad_tar, C, H, W, D, marker);
-    return decnet_launch_status();
+int launch_row(const SpaBwd &a, int marker) {
+    if ((double)a.C * a.H * a.W >= 2147483648.0) return DECNET_ERR_UNSUPPORTED;  // 32-bit element offsets inside a sample
+    return decnet_launch(spamat_bwd_rowb<NT, CB>, dim3((unsigned)((size_t)a.B * a.H)), dim3(64 * RB_NW), 0, a.stream, a.ref,
+                         a.tar, a.rmask, a.tmask, a.out, a.sum_sim, a.max_cost, a.grad_out, a.grad_ref, a.grad_tar, a.C, a.H,
+                         a.W, a.D, marker);
 }
 
 template <int NT, bool VAR, int KQ>
-int launch_both(const float *ref, const float *tar, const float *rmask, const float *tmask,
-                const float *disparity, const float *out, const float *sum_sim, const float *max_cost,
-                const float *grad_out, float *grad_ref, float *grad_tar, float *grad_disp, int B, int C,
-                int H, int W, int D, hipStream_t stream) {
+int launch_both(const SpaBwd &a) {
+    const int B = a.B, C = a.C, H = a.H, W = a.W, D = a.D;
     const int xt0 = side_xt<NT, VAR, 0>(4 * KQ, W), xt1 = side_xt<NT, VAR, 1>(4 * KQ, W);
     if (!xt0 || !xt1) return DECNET_ERR_UNSUPPORTED;
     // sparse rows first (C <= 24, rows of <= 2048 pixels), the rest by the marker launches
@@ -1195,23 +1181,13 @@ int launch_both(const float *ref, const float *tar, const float *rmask, const fl
             marker = 1;
             const int ppt = W <= 1024 ? 4 : 8;
             const size_t slds = 4 * sb_words(KQ, ppt, SB_CAP, SB_THREADS);
-            if (slds > 64 * 1024) {
-                hipError_t e = ppt == 4
-                    ? hipFuncSetAttribute((const void *)spamat_bwd_sparse<VAR, KQ, 4>,
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)slds)
-                    : hipFuncSetAttribute((const void *)spamat_bwd_sparse<VAR, KQ, 8>,
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)slds);
-                if (e != hipSuccess) return (int)e;
-            }
-            if (ppt == 4)
-                hipLaunchKernelGGL((spamat_bwd_sparse<VAR, KQ, 4>), dim3((unsigned)(B * H)), dim3(SB_THREADS), slds,
-                                   stream, ref, tar, rmask, tmask, disparity, out, sum_sim, max_cost, grad_out,
-                                   grad_ref, grad_tar, grad_disp, C, H, W, D, xt0 * 16, xt1 * 16);
-            else
-                hipLaunchKernelGGL((spamat_bwd_sparse<VAR, KQ, 8>), dim3((unsigned)(B * H)), dim3(SB_THREADS), slds,
-                                   stream, ref, tar, rmask, tmask, disparity, out, sum_sim, max_cost, grad_out,
-                                   grad_ref, grad_tar, grad_disp, C, H, W, D, xt0 * 16, xt1 * 16);
-            int rc = decnet_launch_status();
+            auto sparse = [&](auto kernel, int nthr, size_t lds) {       // one sparse-row launch
+                return decnet_launch(kernel, dim3((unsigned)(B * H)), dim3(nthr), lds, a.stream, a.ref, a.tar, a.rmask, a.tmask,
+                                     a.disparity, a.out, a.sum_sim, a.max_cost, a.grad_out, a.grad_ref, a.grad_tar, a.grad_disp,
+                                     C, H, W, D, xt0 * 16, xt1 * 16);
+            };
+            int rc = ppt == 4 ? sparse(spamat_bwd_sparse<VAR, KQ, 4>, SB_THREADS, slds)
+                              : sparse(spamat_bwd_sparse<VAR, KQ, 8>, SB_THREADS, slds);
             if (rc) return rc;
             // rows of 257 - 640 active pixels per side (C <= 8, whole rows of <= 1024 pixels): the same algorithm with
             // 640 slots on 512 threads, on the marked rows only (DECNET_SPAMAT_MID=0 leaves them to the band launches)
@@ -1219,15 +1195,8 @@ int launch_both(const float *ref, const float *tar, const float *rmask, const fl
             if constexpr (KQ == 2) {
                 const size_t mlds = 4 * sb_words(KQ, 4, SBM_CAP, SBM_THREADS);
                 if (!mid_off && ppt == 4 && mlds <= DECNET_LDS_BYTES / 2) {
-                    if (mlds > 64 * 1024) {
-                        hipError_t e = hipFuncSetAttribute((const void *)spamat_bwd_sparse<VAR, KQ, 4, SBM_CAP, SBM_THREADS, true>,
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlds);
-                        if (e != hipSuccess) return (int)e;
-                    }
-                    hipLaunchKernelGGL((spamat_bwd_sparse<VAR, KQ, 4, SBM_CAP, SBM_THREADS, true>), dim3((unsigned)(B * H)),
-                                       dim3(SBM_THREADS), mlds, stream, ref, tar, rmask, tmask, disparity, out, sum_sim,
-                                       max_cost, grad_out, grad_ref, grad_tar, grad_disp, C, H, W, D, xt0 * 16, xt1 * 16);
-                    if ((rc = decnet_launch_status())) return rc;
+                    rc = sparse(spamat_bwd_sparse<VAR, KQ, 4, SBM_CAP, SBM_THREADS, true>, SBM_THREADS, mlds);
+                    if (rc) return rc;
                 }
             }
         }
@@ -1235,64 +1204,44 @@ int launch_both(const float *ref, const float *tar, const float *rmask, const fl
     // dense rows at C <= 8 (SpaMat): both gradients from one pass, four waves per row (the band launch below stays
     // the path of SpaVar, of C > 8 and of rows narrower than the band)
     if constexpr (KQ == 2 && !VAR && NT <= 15) {
-        if (W >= 16 * NT)
-            return launch_row<NT, 1>(ref, tar, rmask, tmask, out, sum_sim, max_cost, grad_out, grad_ref, grad_tar, B, C, H, W,
-                                     D, marker, stream);
+        if (W >= 16 * NT) return launch_row<NT, 1>(a, marker);
     }
     // ... and at 9 - 24 channels (stage 2) with two / three channel blocks (round 6)
     if constexpr (KQ == 6 && !VAR && NT <= 11) {
         if (W >= 16 * NT) {
-            int rc = C <= 16 ? launch_row<NT, 2>(ref, tar, rmask, tmask, out, sum_sim, max_cost, grad_out, grad_ref, grad_tar, B, C,
-                                                H, W, D, marker, stream)
-                             : launch_row<NT, 3>(ref, tar, rmask, tmask, out, sum_sim, max_cost, grad_out, grad_ref, grad_tar, B, C,
-                                                H, W, D, marker, stream);
+            int rc = C <= 16 ? launch_row<NT, 2>(a, marker) : launch_row<NT, 3>(a, marker);
             if (rc != DECNET_ERR_UNSUPPORTED) return rc;
         }
     }
-    return launch_sides<NT, VAR, KQ>(ref, tar, rmask, tmask, disparity, out, sum_sim, max_cost, grad_out, grad_ref,
-                                     grad_tar, grad_disp, B, C, H, W, D, xt0, xt1, marker, stream);
+    return launch_sides<NT, VAR, KQ>(a, xt0, xt1, marker);
 }
 
+// the channel bucket: KQ = its channel count / 4
 template <int NT, bool VAR>
-int launch_c(const float *ref, const float *tar, const float *rmask, const float *tmask,
-             const float *disparity, const float *out, const float *sum_sim, const float *max_cost,
-             const float *grad_out, float *grad_ref, float *grad_tar, float *grad_disp, int B, int C,
-             int H, int W, int D, hipStream_t stream) {
-#define GO(K)                                                                                       \
-    return launch_both<NT, VAR, K>(ref, tar, rmask, tmask, disparity, out, sum_sim, max_cost,      \
-                                   grad_out, grad_ref, grad_tar, grad_disp, B, C, H, W, D, stream)
-    if (C <= 8) GO(2);
-    if (C <= 24) GO(6);
-    if (C <= 72) GO(18);
-#undef GO
+int launch_c(const SpaBwd &a) {
+    if (a.C <= 8) return launch_both<NT, VAR, 2>(a);
+    if (a.C <= 24) return launch_both<NT, VAR, 6>(a);
+    if (a.C <= 72) return launch_both<NT, VAR, 18>(a);
     return DECNET_ERR_UNSUPPORTED;
+}
+
+template <int NT>
+int launch_var(const SpaBwd &a) {
+    return a.var ? launch_c<NT, true>(a) : launch_c<NT, false>(a);
 }
 
 }  // namespace
 
-// var: 0 SpaMat, 1 SpaVar (also writes grad_disp).  DECNET_ERR_UNSUPPORTED (C > 72, band wider
+// a.var: 0 SpaMat, 1 SpaVar (also writes grad_disp).  DECNET_ERR_UNSUPPORTED (C > 72, band wider
 // than 18 tiles, LDS overflow) makes capi.hip fall back to the row-tile kernels.
-int decnet_mfma_backward(int var, const float *ref, const float *tar, const float *rmask,
-                         const float *tmask, const float *disparity, const float *out,
-                         const float *sum_sim, const float *max_cost, const float *grad_out,
-                         float *grad_ref, float *grad_tar, float *grad_disp, int B, int C, int H,
-                         int W, int max_disp, hipStream_t stream) {
-    const int D = max_disp;
+int decnet_mfma_backward(const SpaBwd &a) {
+    const int D = a.D;
     const int need = D <= 1 ? 1 : (D - 1 + 15) / 16 + 1;
     if (need > 18) return DECNET_ERR_UNSUPPORTED;
     // the band loop is a runtime loop (nothing is kept per tile), so NT only sizes the halo
-#define GO(N)                                                                                       \
-    do {                                                                                            \
-        if (var)                                                                                    \
-            return launch_c<N, true>(ref, tar, rmask, tmask, disparity, out, sum_sim, max_cost,     \
-                                     grad_out, grad_ref, grad_tar, grad_disp, B, C, H, W, D, stream); \
-        return launch_c<N, false>(ref, tar, rmask, tmask, disparity, out, sum_sim, max_cost,        \
-                                  grad_out, grad_ref, grad_tar, grad_disp, B, C, H, W, D, stream);  \
-    } while (0)
-    if (need <= 3) GO(3);
-    if (need <= 6) GO(6);
-    if (need <= 11) GO(11);
-    if (need <= 15) GO(15);
-    GO(18);
-#undef GO
+    if (need <= 3) return launch_var<3>(a);
+    if (need <= 6) return launch_var<6>(a);
+    if (need <= 11) return launch_var<11>(a);
+    if (need <= 15) return launch_var<15>(a);
+    return launch_var<18>(a);
 }

@@ -34,9 +34,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <type_traits>
-
-#include "common.h"
+#include "spamat_host.h"
 
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -44,8 +42,6 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
-
-enum { MODE_MAT = 0, MODE_VAR = 1, MODE_FUSED = 2 };
 
 constexpr float NEG_BIG = -1.0e30f;
 constexpr float LOG2E = 1.4426950408889634f;
@@ -1407,9 +1403,8 @@ __global__ __launch_bounds__(SP_THREADS, PPT == 4 ? 6 : 5) void spamat_fwd_spars
 }
 
 template <int NT, int KQ>
-int launch_nt(int mode, const float *ref, const float *tar, const float *rmask, const float *tmask,
-              const float *disparity, float *out, float *var_out, float *sum_sim, float *max_cost,
-              int B, int C, int H, int W, int D, int allow_compact, int mbits, hipStream_t stream) {
+int launch_nt(const SpaFwd &a) {
+    const int B = a.B, C = a.C, H = a.H, W = a.W, D = a.D, allow_compact = a.allow_compact, mbits = a.mbits;
     const int xt_row = ceil_div(W, 16);
     // dense rows on the bf16 matrix cores (dense16_body) for the shipped channel counts (C = 8, 24) unless
     // DECNET_SPAMAT_DENSE=fp32 or the compaction paths are pinned off; it needs more LDS per staged position
@@ -1469,94 +1464,49 @@ int launch_nt(int mode, const float *ref, const float *tar, const float *rmask, 
     if constexpr (KQ > 0 && KQ <= 6) if (marker) {
         const int ppt = W <= 1024 ? 4 : 8;
         const size_t slds = 4 * sparse_row_words(KQ, ppt, SP_THREADS, SP_CAP);
-#define LAUNCHS(M, P)                                                                              \
-    do {                                                                                           \
-        if (slds > 64 * 1024) {                                                                    \
-            hipError_t e = hipFuncSetAttribute((const void *)spamat_fwd_sparse<NT, M, (KQ ? KQ : 1), P>, \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)slds); \
-            if (e != hipSuccess) return (int)e;                                                    \
-        }                                                                                          \
-        hipLaunchKernelGGL((spamat_fwd_sparse<NT, M, (KQ ? KQ : 1), P>), dim3((unsigned)(B * H)),  \
-                           dim3(SP_THREADS), slds, stream, ref, tar, rmask, tmask, disparity, out, \
-                           var_out, sum_sim, max_cost, C, H, W, D, XT * 16, sparse_pct, mbits, handover); \
-    } while (0)
-#define LAUNCHSP(M)                                                                                \
-    do {                                                                                           \
-        if (ppt == 4) LAUNCHS(M, 4);                                                               \
-        else LAUNCHS(M, 8);                                                                        \
-    } while (0)
-        if (mode == MODE_MAT) LAUNCHSP(MODE_MAT);
-        else if (mode == MODE_VAR) LAUNCHSP(MODE_VAR);
-        else LAUNCHSP(MODE_FUSED);
-#undef LAUNCHSP
-#undef LAUNCHS
-        int rc = decnet_launch_status();
+        int rc = spamat_with_mode(a.mode, [&](auto M) {
+            return spamat_with_flag(ppt == 4, [&](auto P4) {
+                return decnet_launch(spamat_fwd_sparse<NT, M(), KQ, (P4() ? 4 : 8)>, dim3((unsigned)(B * H)), dim3(SP_THREADS),
+                                     slds, a.stream, a.ref, a.tar, a.rmask, a.tmask, a.disparity, a.out, a.var_out, a.sum_sim,
+                                     a.max_cost, C, H, W, D, XT * 16, sparse_pct, mbits, handover);
+            });
+        });
         if (rc) return rc;
     }
-#define LAUNCH1(M, DD)                                                                             \
-    do {                                                                                           \
-        if (lds_launch > 64 * 1024) {                                                              \
-            hipError_t e = hipFuncSetAttribute((const void *)spamat_fwd_mfma<NT, M, KQ, DD>,       \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_launch); \
-            if (e != hipSuccess) return (int)e;                                                    \
-        }                                                                                          \
-        hipLaunchKernelGGL((spamat_fwd_mfma<NT, M, KQ, DD>), grid, block, lds_launch, stream, ref, tar, rmask, \
-                           tmask, disparity, out, var_out, sum_sim, max_cost, C, H, W, D, segs, XT, \
-                           allow_compact, marker, compact_pct, handover ? 2 : mbits);              \
-    } while (0)
-#define LAUNCH(M)                                                                                  \
-    do {                                                                                           \
-        if constexpr (KQ == 2) {                                                                   \
-            if (d16) LAUNCH1(M, true);                                                             \
-            else LAUNCH1(M, false);                                                                \
-        } else {                                                                                   \
-            LAUNCH1(M, false);                                                                     \
-        }                                                                                          \
-    } while (0)
-    if (mode == MODE_MAT) LAUNCH(MODE_MAT);
-    else if (mode == MODE_VAR) LAUNCH(MODE_VAR);
-    else LAUNCH(MODE_FUSED);
-#undef LAUNCH1
-#undef LAUNCH
-    return decnet_launch_status();
+    auto band = [&](auto M, auto D16) {
+        return decnet_launch(spamat_fwd_mfma<NT, M(), KQ, D16()>, grid, block, lds_launch, a.stream, a.ref, a.tar, a.rmask,
+                             a.tmask, a.disparity, a.out, a.var_out, a.sum_sim, a.max_cost, C, H, W, D, segs, XT,
+                             allow_compact, marker, compact_pct, handover ? 2 : mbits);
+    };
+    return spamat_with_mode(a.mode, [&](auto M) {
+        if constexpr (KQ == 2) return spamat_with_flag(d16, [&](auto D16) { return band(M, D16); });
+        else return band(M, std::false_type{});
+    });
 }
 
+// the channel bucket: KQ = its channel count / 4 (0: any C)
 template <int NT>
-int launch_kq(int mode, const float *ref, const float *tar, const float *rmask, const float *tmask,
-              const float *disparity, float *out, float *var_out, float *sum_sim, float *max_cost,
-              int B, int C, int H, int W, int D, int allow_compact, int mbits, hipStream_t stream) {
-#define GO(K)                                                                                      \
-    return launch_nt<NT, K>(mode, ref, tar, rmask, tmask, disparity, out, var_out, sum_sim,        \
-                            max_cost, B, C, H, W, D, allow_compact, mbits, stream)
-    if (C <= 8 && C > 4) GO(2);        // stage 3 of the shipped network (C = 8)
-    if (C <= 24 && C > 20) GO(6);      // stage 2 (C = 24)
-    if (C <= 72 && C > 68) GO(18);     // stage 1 (C = 72)
-    GO(0);                             // anything else: runtime K loop, left operand read straight
-                                       // from L2/HBM per K-step
-#undef GO
+int launch_kq(const SpaFwd &a) {
+    const int C = a.C;
+    if (C <= 8 && C > 4) return launch_nt<NT, 2>(a);        // stage 3 of the shipped network (C = 8)
+    if (C <= 24 && C > 20) return launch_nt<NT, 6>(a);      // stage 2 (C = 24)
+    if (C <= 72 && C > 68) return launch_nt<NT, 18>(a);     // stage 1 (C = 72)
+    return launch_nt<NT, 0>(a);                             // anything else: runtime K loop, left operand read straight
+                                                            // from L2/HBM per K-step
 }
 
 }  // namespace
 
-// mode: 0 SpaMat, 1 SpaVar, 2 fused.  Returns DECNET_ERR_UNSUPPORTED when the band needs more
-// than 18 tiles (max_disp > 273) or a tile does not fit LDS; the dispatcher in capi.hip then
-// uses the row-tile kernel.  allow_compact = 0 pins the dense path (A/B benchmarks, tests).
-// mbits = 1: rmask / tmask point at bit-packed masks ([B,H,ceil(W/64)] 64-bit words, decnet_detail_mask's layout).
-int decnet_mfma_forward(int mode, const float *ref, const float *tar, const float *rmask,
-                        const float *tmask, const float *disparity, float *out, float *var_out,
-                        float *sum_sim, float *max_cost, int B, int C, int H, int W, int max_disp,
-                        int allow_compact, int mbits, hipStream_t stream) {
-    const int D = max_disp;
+// Returns DECNET_ERR_UNSUPPORTED when the band needs more than 18 tiles (max_disp > 273) or a tile does not fit LDS; the
+// dispatcher in capi.hip then uses the row-tile kernel.  The record's fields: spamat_host.h.
+int decnet_mfma_forward(const SpaFwd &a) {
+    const int D = a.D;
     const int need = D <= 1 ? 1 : (D - 1 + 15) / 16 + 1;
-#define GO(N)                                                                                     \
-    return launch_kq<N>(mode, ref, tar, rmask, tmask, disparity, out, var_out, sum_sim, max_cost, \
-                        B, C, H, W, D, allow_compact, mbits, stream)
-    if (need <= 3) GO(3);       // D <= 33   (stage 1: 24, 30)
-    if (need <= 6) GO(6);       // D <= 81   (stage 2: 72)
-    if (need <= 8) GO(8);       // D <= 113  (stage 2 at max_disp 270: 90)
-    if (need <= 11) GO(11);     // D <= 161
-    if (need <= 15) GO(15);     // D <= 225  (stage 3: 216)
-    if (need <= 18) GO(18);     // D <= 273  (stage 3 at max_disp 270)
+    if (need <= 3) return launch_kq<3>(a);       // D <= 33   (stage 1: 24, 30)
+    if (need <= 6) return launch_kq<6>(a);       // D <= 81   (stage 2: 72)
+    if (need <= 8) return launch_kq<8>(a);       // D <= 113  (stage 2 at max_disp 270: 90)
+    if (need <= 11) return launch_kq<11>(a);     // D <= 161
+    if (need <= 15) return launch_kq<15>(a);     // D <= 225  (stage 3: 216)
+    if (need <= 18) return launch_kq<18>(a);     // D <= 273  (stage 3 at max_disp 270)
     return DECNET_ERR_UNSUPPORTED;
-#undef GO
 }

@@ -18,11 +18,9 @@
 // Arithmetic follows the reference statement by statement (floors, 1e-6 seeds, d order,
 // fmaf chain over channels as nvcc contracts it) so results agree with oracle/ to
 // rounding; see tests/test_spamat_gpu.py for the stated tolerances.
-#include "common.h"
+#include "spamat_host.h"
 
 namespace {
-
-enum { MODE_MAT = 0, MODE_VAR = 1, MODE_FUSED = 2 };
 
 struct RowTile {
     int b, y, x0, row;
@@ -307,24 +305,6 @@ int pick_tw(int W, size_t per_tw_floats, size_t fixed_floats, size_t *lds_bytes)
     return 0;
 }
 
-int check_args(const void *const *ptrs, int n, int B, int C, int H, int W, int max_disp) {
-    for (int i = 0; i < n; ++i)
-        if (!ptrs[i]) return DECNET_ERR_NULL_POINTER;
-    if (B < 1 || C < 1 || H < 1 || W < 1 || max_disp < 1) return DECNET_ERR_BAD_SHAPE;
-    if ((double)B * C * H * W >= 2147483648.0) return DECNET_ERR_BAD_SHAPE;
-    return DECNET_OK;
-}
-
-template <typename K>
-int set_lds(K kernel, size_t bytes) {
-    if (bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void *)kernel,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) return (int)e;
-    }
-    return DECNET_OK;
-}
-
 // Last resort of the forward pass (C x max_disp beyond any LDS tile, e.g. C = 216 with max_disp = 270):
 // the arithmetic of spamat_fwd_rowtile straight from global memory, one thread per left pixel.
 template <int MODE>
@@ -444,108 +424,59 @@ __global__ __launch_bounds__(256) void spamat_bwd_generic(
 }  // namespace
 
 // ------------------------------- host launchers (internal) ------------------------------
-// mode: 0 SpaMat, 1 SpaVar, 2 fused.  Used by capi.hip.
+// Used by capi.hip (spamat_host.h).
 
-int decnet_rowtile_forward(int mode, const float *ref, const float *tar, const float *rmask,
-                           const float *tmask, const float *disparity, float *out, float *var_out,
-                           float *sum_sim, float *max_cost, int B, int C, int H, int W, int max_disp,
-                           hipStream_t stream) {
-    const int D = max_disp;
+int decnet_rowtile_forward(const SpaFwd &a) {
+    const int C = a.C, W = a.W, D = a.D;
     size_t lds = 0;
     // Ls C*TW + Rs C*(TW+D-1) + Ts (TW+D-1)
     int TW = pick_tw(W, (size_t)2 * C + 1, (size_t)(C + 1) * (D - 1), &lds);
     if (!TW) {                                          // no LDS tile fits: global-memory kernel
-        const size_t n = (size_t)B * H * W;
+        const size_t n = (size_t)a.B * a.H * W;
         const dim3 g((unsigned)((n + 255) / 256)), blk(256);
-        if (mode == MODE_MAT)
-            hipLaunchKernelGGL(spamat_fwd_generic<MODE_MAT>, g, blk, 0, stream, ref, tar, rmask, tmask, disparity, out,
-                               var_out, sum_sim, max_cost, B, C, H, W, D);
-        else if (mode == MODE_VAR)
-            hipLaunchKernelGGL(spamat_fwd_generic<MODE_VAR>, g, blk, 0, stream, ref, tar, rmask, tmask, disparity, out,
-                               var_out, sum_sim, max_cost, B, C, H, W, D);
-        else
-            hipLaunchKernelGGL(spamat_fwd_generic<MODE_FUSED>, g, blk, 0, stream, ref, tar, rmask, tmask, disparity, out,
-                               var_out, sum_sim, max_cost, B, C, H, W, D);
-        return decnet_launch_status();
+        return spamat_with_mode(a.mode, [&](auto M) {
+            return decnet_launch(spamat_fwd_generic<M()>, g, blk, 0, a.stream, a.ref, a.tar, a.rmask, a.tmask, a.disparity,
+                                 a.out, a.var_out, a.sum_sim, a.max_cost, a.B, C, a.H, W, D);
+        });
     }
     int tiles = ceil_div(W, TW);
-    dim3 grid((unsigned)((size_t)B * H * tiles)), block(TW);
-    int rc;
-#define LAUNCH(M)                                                                              \
-    rc = set_lds(spamat_fwd_rowtile<M>, lds);                                                  \
-    if (rc) return rc;                                                                         \
-    hipLaunchKernelGGL(spamat_fwd_rowtile<M>, grid, block, lds, stream, ref, tar, rmask, tmask, \
-                       disparity, out, var_out, sum_sim, max_cost, C, H, W, D, tiles)
-    if (mode == MODE_MAT) { LAUNCH(MODE_MAT); }
-    else if (mode == MODE_VAR) { LAUNCH(MODE_VAR); }
-    else { LAUNCH(MODE_FUSED); }
-#undef LAUNCH
-    return decnet_launch_status();
+    dim3 grid((unsigned)((size_t)a.B * a.H * tiles)), block(TW);
+    return spamat_with_mode(a.mode, [&](auto M) {
+        return decnet_launch(spamat_fwd_rowtile<M()>, grid, block, lds, a.stream, a.ref, a.tar, a.rmask, a.tmask,
+                             a.disparity, a.out, a.var_out, a.sum_sim, a.max_cost, C, a.H, W, D, tiles);
+    });
 }
 
-int decnet_rowtile_backward(int var, const float *ref, const float *tar, const float *rmask,
-                            const float *tmask, const float *disparity, const float *out,
-                            const float *sum_sim, const float *max_cost, const float *grad_out,
-                            float *grad_ref, float *grad_tar, float *grad_disp, int B, int C, int H,
-                            int W, int max_disp, hipStream_t stream) {
-    const int D = max_disp;
+int decnet_rowtile_backward(const SpaBwd &a) {
+    const int C = a.C, W = a.W, D = a.D;
     size_t lds_r = 0, lds_t = 0;
     int TWr = pick_tw(W, (size_t)2 * C + 1 + D, (size_t)(C + 1) * (D - 1), &lds_r);
-    int planes = var ? 5 : 4;
+    int planes = a.var ? 5 : 4;
     int TWt = pick_tw(W, (size_t)2 * C + planes + D, (size_t)(C + planes) * (D - 1), &lds_t);
     if (!TWr || !TWt) {                                 // C x max_disp beyond any LDS tile: global-memory kernels
-        const size_t n = (size_t)B * H * W;
+        const size_t n = (size_t)a.B * a.H * W;
         if (n >= ((size_t)1 << 31) * 256) return DECNET_ERR_BAD_SHAPE;
         const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-        if (var) {
-            hipLaunchKernelGGL((spamat_bwd_generic<true, 0>), grid, block, 0, stream, ref, tar, rmask, tmask, disparity,
-                               out, sum_sim, max_cost, grad_out, grad_ref, grad_disp, B, C, H, W, D);
-            hipLaunchKernelGGL((spamat_bwd_generic<true, 1>), grid, block, 0, stream, ref, tar, rmask, tmask, disparity,
-                               out, sum_sim, max_cost, grad_out, grad_tar, nullptr, B, C, H, W, D);
-        } else {
-            hipLaunchKernelGGL((spamat_bwd_generic<false, 0>), grid, block, 0, stream, ref, tar, rmask, tmask, disparity,
-                               out, sum_sim, max_cost, grad_out, grad_ref, nullptr, B, C, H, W, D);
-            hipLaunchKernelGGL((spamat_bwd_generic<false, 1>), grid, block, 0, stream, ref, tar, rmask, tmask, disparity,
-                               out, sum_sim, max_cost, grad_out, grad_tar, nullptr, B, C, H, W, D);
-        }
-        return decnet_launch_status();
+        return spamat_with_flag(a.var, [&](auto VAR) {
+            if (int rc = decnet_launch(spamat_bwd_generic<VAR(), 0>, grid, block, 0, a.stream, a.ref, a.tar, a.rmask, a.tmask,
+                                       a.disparity, a.out, a.sum_sim, a.max_cost, a.grad_out, a.grad_ref,
+                                       VAR() ? a.grad_disp : nullptr, a.B, C, a.H, W, D))
+                return rc;
+            return decnet_launch(spamat_bwd_generic<VAR(), 1>, grid, block, 0, a.stream, a.ref, a.tar, a.rmask, a.tmask,
+                                 a.disparity, a.out, a.sum_sim, a.max_cost, a.grad_out, a.grad_tar, nullptr, a.B, C, a.H, W, D);
+        });
     }
-    int rc;
-    {
-        int tiles = ceil_div(W, TWr);
-        dim3 grid((unsigned)((size_t)B * H * tiles)), block(TWr);
-        if (var) {
-            if ((rc = set_lds(spamat_bwd_ref_rowtile<true>, lds_r))) return rc;
-            hipLaunchKernelGGL(spamat_bwd_ref_rowtile<true>, grid, block, lds_r, stream, ref, tar,
-                               rmask, tmask, disparity, out, sum_sim, max_cost, grad_out, grad_ref,
-                               grad_disp, C, H, W, D, tiles);
-        } else {
-            if ((rc = set_lds(spamat_bwd_ref_rowtile<false>, lds_r))) return rc;
-            hipLaunchKernelGGL(spamat_bwd_ref_rowtile<false>, grid, block, lds_r, stream, ref, tar,
-                               rmask, tmask, disparity, out, sum_sim, max_cost, grad_out, grad_ref,
-                               grad_disp, C, H, W, D, tiles);
-        }
-        if ((rc = decnet_launch_status())) return rc;
-    }
-    {
-        int tiles = ceil_div(W, TWt);
-        dim3 grid((unsigned)((size_t)B * H * tiles)), block(TWt);
-        if (var) {
-            if ((rc = set_lds(spamat_bwd_tar_rowtile<true>, lds_t))) return rc;
-            hipLaunchKernelGGL(spamat_bwd_tar_rowtile<true>, grid, block, lds_t, stream, ref, tar,
-                               rmask, tmask, disparity, out, sum_sim, max_cost, grad_out, grad_tar,
-                               C, H, W, D, tiles);
-        } else {
-            if ((rc = set_lds(spamat_bwd_tar_rowtile<false>, lds_t))) return rc;
-            hipLaunchKernelGGL(spamat_bwd_tar_rowtile<false>, grid, block, lds_t, stream, ref, tar,
-                               rmask, tmask, disparity, out, sum_sim, max_cost, grad_out, grad_tar,
-                               C, H, W, D, tiles);
-        }
-    }
-    return decnet_launch_status();
-}
-
-int decnet_check_spamat_args(const void *const *ptrs, int n, int B, int C, int H, int W,
-                             int max_disp) {
-    return check_args(ptrs, n, B, C, H, W, max_disp);
+    int tiles = ceil_div(W, TWr);
+    int rc = spamat_with_flag(a.var, [&](auto VAR) {
+        return decnet_launch(spamat_bwd_ref_rowtile<VAR()>, dim3((unsigned)((size_t)a.B * a.H * tiles)), dim3(TWr), lds_r,
+                             a.stream, a.ref, a.tar, a.rmask, a.tmask, a.disparity, a.out, a.sum_sim, a.max_cost, a.grad_out,
+                             a.grad_ref, a.grad_disp, C, a.H, W, D, tiles);
+    });
+    if (rc) return rc;
+    tiles = ceil_div(W, TWt);
+    return spamat_with_flag(a.var, [&](auto VAR) {
+        return decnet_launch(spamat_bwd_tar_rowtile<VAR()>, dim3((unsigned)((size_t)a.B * a.H * tiles)), dim3(TWt), lds_t,
+                             a.stream, a.ref, a.tar, a.rmask, a.tmask, a.disparity, a.out, a.sum_sim, a.max_cost, a.grad_out,
+                             a.grad_tar, C, a.H, W, D, tiles);
+    });
 }

@@ -29,19 +29,11 @@
 //                    straight from the mask bits) and the offset disparity plane;
 //   band_accumulate  one launch per band of the backward: grad_ref += band, grad_tar += band shifted back, grad_disp += band.
 // Every element is one copy, one subtraction of d0 or one addition: the results do not depend on the launch shape.
-#include "common.h"
-
-int decnet_mfma_forward(int mode, const float *ref, const float *tar, const float *rmask, const float *tmask,
-                        const float *disparity, float *out, float *var_out, float *sum_sim, float *max_cost, int B, int C,
-                        int H, int W, int max_disp, int allow_compact, int mbits, hipStream_t stream);
-int decnet_mfma_backward(int var, const float *ref, const float *tar, const float *rmask, const float *tmask,
-                         const float *disparity, const float *out, const float *sum_sim, const float *max_cost,
-                         const float *grad_out, float *grad_ref, float *grad_tar, float *grad_disp, int B, int C, int H,
-                         int W, int max_disp, hipStream_t stream);
+#include "spamat_host.h"
 
 namespace {
 
-constexpr int WIDE_BAND = 272;          // widest band of the matrix-core kernels (18 tiles)
+constexpr int WIDE_BAND = SPAMAT_BAND_DISP;      // widest band a sweep hands to the matrix-core kernels
 constexpr int EW_THREADS = 256;
 
 constexpr int ROW_WAVES = EW_THREADS / DECNET_WAVE;      // rows a workgroup works on at a time (one per wave)
@@ -228,7 +220,6 @@ struct Scratch {
         int rc_ = (expr);                     \
         if (rc_) return rc_;                  \
     } while (0)
-#define LAUNCH_OK() CK(decnet_launch_status())
 
 // planes of np = B H W floats a forward sweep needs: the shifted right features (C), the shifted right mask, the band's
 // (q, S, m); + the offset disparity (SpaVar) / the band's variance (fused); + the unpacked left mask (bit-mask entry)
@@ -249,108 +240,125 @@ size_t decnet_wide_workspace_floats(int B, int C, int H, int W, int D, int which
     return forward_planes(C, which == 3 ? 2 : which, which == 3) * np;
 }
 
-// mode 0 SpaMat (out, S, m), 1 SpaVar (var_out, S, m; `disparity` given), 2 fused (out, var_out, S, m).
-// mbits: the masks are bit-packed (decnet_spamatvar_forward_bits): the left mask is unpacked into a scratch plane once, the
+// a.mode 0 SpaMat (out, S, m), 1 SpaVar (var_out, S, m; `disparity` given), 2 fused (out, var_out, S, m).
+// a.mbits: the masks are bit-packed (decnet_spamatvar_forward_bits): the left mask is unpacked into a scratch plane once, the
 // right mask per band straight into its shifted form.
 // ws: the caller's workspace (decnet_wide_workspace_floats floats, checked by capi.hip), or nullptr: allocate, and decline
 // while the stream is being captured.
-int decnet_wide_forward(int mode, const float *ref, const float *tar, const float *rmask, const float *tmask,
-                        const float *disparity, float *out, float *var_out, float *sum_sim, float *max_cost, int B, int C,
-                        int H, int W, int D, int allow_compact, int mbits, float *ws, hipStream_t stream) {
+int decnet_wide_forward(const SpaFwd &a, float *ws) {
+    const int C = a.C, W = a.W, D = a.D;
+    hipStream_t stream = a.stream;
     if (D <= WIDE_BAND) return DECNET_ERR_UNSUPPORTED;
     if (!ws && capturing(stream)) return DECNET_ERR_UNSUPPORTED;
     const int nb = ceil_div(D, WIDE_BAND), Db = ceil_div(D, nb), wpr = (W + 63) >> 6;
-    const size_t np = (size_t)B * H * W, rowsF = (size_t)B * C * H, rowsM = (size_t)B * H;
+    const size_t np = (size_t)a.B * a.H * W, rowsF = (size_t)a.B * C * a.H, rowsM = (size_t)a.B * a.H;
     Scratch sc(stream);
-    CK(sc.get(ws, forward_planes(C, mode, mbits) * np));
+    CK(sc.get(ws, forward_planes(C, a.mode, a.mbits) * np));
     float *Rb = sc.p, *tmb = Rb + (size_t)C * np, *qb = tmb + np, *Sb = qb + np, *mb = Sb + np, *db = mb + np,
-          *rmf = db + (mode ? np : 0);                                  // db: modes 1, 2 only; rmf: mbits only
-    const void *tsrc = tmask;                                           // the right mask as the caller gave it
-    const int tkind = mbits ? ROW_BITS : ROW_SHIFT;
-    if (mbits) {                                                        // band 0 reads float planes like every other band
-        const RowJobs jobs = {{row_job(ROW_BITS, rmask, rmf, rowsM, 0), row_job(ROW_BITS, tmask, tmb, rowsM, 0), RowJob{}}};
-        hipLaunchKernelGGL(band_stage, dim3(row_grid(jobs)), dim3(EW_THREADS), 0, stream, jobs, W, wpr);
-        LAUNCH_OK();
-        rmask = rmf;
-        tmask = tmb;
+          *rmf = db + (a.mode ? np : 0);                                // db: modes 1, 2 only; rmf: mbits only
+    const void *tsrc = a.tmask;                                         // the right mask as the caller gave it
+    const int tkind = a.mbits ? ROW_BITS : ROW_SHIFT;
+    SpaFwd band = a;                                                    // a band call: this call on float masks, fields set per band
+    band.mbits = 0;
+    if (a.mbits) {                                                      // band 0 reads float planes like every other band
+        const RowJobs jobs = {{row_job(ROW_BITS, a.rmask, rmf, rowsM, 0), row_job(ROW_BITS, a.tmask, tmb, rowsM, 0), RowJob{}}};
+        CK(decnet_launch(band_stage, dim3(row_grid(jobs)), dim3(EW_THREADS), 0, stream, jobs, W, wpr));
+        band.rmask = rmf;
+        band.tmask = tmb;
     }
+    const float *rmask = band.rmask, *tmask = band.tmask;               // float planes from here on
     // band b > 0 of a sweep: (Rb, tmb[, db = disp - d0]) in one launch
     auto stage = [&](int d0, const float *disp) -> int {
-        const RowJobs jobs = {{row_job(ROW_SHIFT, tar, Rb, rowsF, d0), row_job(tkind, tsrc, tmb, rowsM, d0),
+        const RowJobs jobs = {{row_job(ROW_SHIFT, a.tar, Rb, rowsF, d0), row_job(tkind, tsrc, tmb, rowsM, d0),
                                disp ? row_job(ROW_OFFSET, disp, db, rowsM, 0, (float)d0) : RowJob{}}};
-        hipLaunchKernelGGL(band_stage, dim3(row_grid(jobs)), dim3(EW_THREADS), 0, stream, jobs, W, wpr);
-        return decnet_launch_status();
+        return decnet_launch(band_stage, dim3(row_grid(jobs)), dim3(EW_THREADS), 0, stream, jobs, W, wpr);
     };
     // one sweep over the bands for a quotient q in {disparity (SpaMat), variance (SpaVar)}: band 0 lands in (q, S, m)
     // itself, the others in (qb, Sb, mb) and are merged in
     auto sweep = [&](int var, const float *disp, float *q, float *S, float *m) -> int {
+        band.mode = var ? MODE_VAR : MODE_MAT;
         for (int b = 0; b < nb; ++b) {
             const int d0 = b * Db, dw = (D - d0 < Db) ? D - d0 : Db;
-            const float *Rv = tar, *tv = tmask, *dv = disp;
+            const float *Rv = a.tar, *tv = tmask, *dv = disp;
             if (b) {
                 CK(stage(d0, var ? disp : nullptr));
                 Rv = Rb; tv = tmb; dv = db;
             }
             float *qo = b ? qb : q, *So = b ? Sb : S, *mo = b ? mb : m;
-            CK(decnet_mfma_forward(var ? 1 : 0, ref, Rv, rmask, tv, var ? dv : nullptr, var ? nullptr : qo, var ? qo : nullptr,
-                                   So, mo, B, C, H, W, dw, allow_compact, 0, stream));
-            if (b) {
-                hipLaunchKernelGGL(merge_band, dim3(ew_grid(np)), dim3(EW_THREADS), 0, stream, rmask, q, S, m, qb, Sb, mb, np,
-                                   var ? 0.f : (float)d0);
-                LAUNCH_OK();
-            }
+            band.tar = Rv;
+            band.tmask = tv;
+            band.disparity = var ? dv : nullptr;
+            band.out = var ? nullptr : qo;
+            band.var_out = var ? qo : nullptr;
+            band.sum_sim = So;
+            band.max_cost = mo;
+            band.D = dw;
+            CK(decnet_mfma_forward(band));
+            if (b)
+                CK(decnet_launch(merge_band, dim3(ew_grid(np)), dim3(EW_THREADS), 0, stream, rmask, q, S, m, qb, Sb, mb, np,
+                                 var ? 0.f : (float)d0));
         }
         return 0;
     };
-    if (mode == 1) return sweep(1, disparity, var_out, sum_sim, max_cost);
-    if (mode == 0) return sweep(0, nullptr, out, sum_sim, max_cost);
+    if (a.mode == MODE_VAR) return sweep(1, a.disparity, a.var_out, a.sum_sim, a.max_cost);
+    if (a.mode == MODE_MAT) return sweep(0, nullptr, a.out, a.sum_sim, a.max_cost);
     // fused: one sweep of fused band calls (each band's variance around its own disparity, in db), merged around the joint mean
+    band.disparity = nullptr;
     for (int b = 0; b < nb; ++b) {
-        const int d0 = b * Db, dw = (D - d0 < Db) ? D - d0 : Db;
+        const int d0 = b * Db;
+        band.D = (D - d0 < Db) ? D - d0 : Db;
         if (!b) {
-            CK(decnet_mfma_forward(2, ref, tar, rmask, tmask, nullptr, out, var_out, sum_sim, max_cost, B, C, H, W, dw,
-                                   allow_compact, 0, stream));
+            CK(decnet_mfma_forward(band));                              // straight into (out, var_out, sum_sim, max_cost)
             continue;
         }
         CK(stage(d0, nullptr));
-        CK(decnet_mfma_forward(2, ref, Rb, rmask, tmb, nullptr, qb, db, Sb, mb, B, C, H, W, dw, allow_compact, 0, stream));
-        hipLaunchKernelGGL(merge_band_fused, dim3(ew_grid(np)), dim3(EW_THREADS), 0, stream, rmask, out, var_out, sum_sim,
-                           max_cost, qb, db, Sb, mb, np, (float)d0);
-        LAUNCH_OK();
+        band.tar = Rb;
+        band.tmask = tmb;
+        band.out = qb;
+        band.var_out = db;
+        band.sum_sim = Sb;
+        band.max_cost = mb;
+        CK(decnet_mfma_forward(band));
+        CK(decnet_launch(merge_band_fused, dim3(ew_grid(np)), dim3(EW_THREADS), 0, stream, rmask, a.out, a.var_out, a.sum_sim,
+                         a.max_cost, qb, db, Sb, mb, np, (float)d0));
     }
     return 0;
 }
 
-// var: 0 SpaMat, 1 SpaVar (also grad_disp).  ws as in decnet_wide_forward.
-int decnet_wide_backward(int var, const float *ref, const float *tar, const float *rmask, const float *tmask,
-                         const float *disparity, const float *out, const float *sum_sim, const float *max_cost,
-                         const float *grad_out, float *grad_ref, float *grad_tar, float *grad_disp, int B, int C, int H,
-                         int W, int D, float *ws, hipStream_t stream) {
+// a.var: 0 SpaMat, 1 SpaVar (also grad_disp).  ws as in decnet_wide_forward.
+int decnet_wide_backward(const SpaBwd &a, float *ws) {
+    const int var = a.var, C = a.C, W = a.W, D = a.D;
+    hipStream_t stream = a.stream;
     if (D <= WIDE_BAND) return DECNET_ERR_UNSUPPORTED;
     if (!ws && capturing(stream)) return DECNET_ERR_UNSUPPORTED;
     const int nb = ceil_div(D, WIDE_BAND), Db = ceil_div(D, nb);
-    const size_t np = (size_t)B * H * W, nf = (size_t)C * np, rowsF = (size_t)B * C * H, rowsM = (size_t)B * H;
+    const size_t np = (size_t)a.B * a.H * W, nf = (size_t)C * np, rowsF = (size_t)a.B * C * a.H, rowsM = (size_t)a.B * a.H;
     Scratch sc(stream);
     CK(sc.get(ws, backward_planes(C, var) * np));
     float *Rb = sc.p, *glb = Rb + nf, *grb = glb + nf, *tmb = grb + nf, *sh = tmb + np, *gdb = sh + np;   // gdb: SpaVar only
+    SpaBwd band = a;                                                    // band 0: this call, narrower
     for (int b = 0; b < nb; ++b) {
-        const int d0 = b * Db, dw = (D - d0 < Db) ? D - d0 : Db;
+        const int d0 = b * Db;
+        band.D = (D - d0 < Db) ? D - d0 : Db;
         if (!b) {
-            CK(decnet_mfma_backward(var, ref, tar, rmask, tmask, disparity, out, sum_sim, max_cost, grad_out, grad_ref, grad_tar,
-                                    grad_disp, B, C, H, W, dw, stream));
+            CK(decnet_mfma_backward(band));
             continue;
         }
         // the plane that is a disparity moves with the band: SpaMat's output (SM_kernel.cu:191), SpaVar's input (SV_kernel.cu:191)
-        const RowJobs in = {{row_job(ROW_SHIFT, tar, Rb, rowsF, d0), row_job(ROW_SHIFT, tmask, tmb, rowsM, d0),
-                             row_job(ROW_OFFSET, var ? disparity : out, sh, rowsM, 0, (float)d0)}};
-        hipLaunchKernelGGL(band_stage, dim3(row_grid(in)), dim3(EW_THREADS), 0, stream, in, W, 0);
-        LAUNCH_OK();
-        CK(decnet_mfma_backward(var, ref, Rb, rmask, tmb, var ? sh : nullptr, var ? out : sh, sum_sim, max_cost, grad_out, glb, grb,
-                                var ? gdb : nullptr, B, C, H, W, dw, stream));
-        const RowJobs acc = {{row_job(ROW_ADD, glb, grad_ref, rowsF, 0), row_job(ROW_ADD, grb, grad_tar, rowsF, d0),
-                              var ? row_job(ROW_ADD, gdb, grad_disp, rowsM, 0) : RowJob{}}};
-        hipLaunchKernelGGL(band_accumulate, dim3(row_grid(acc)), dim3(EW_THREADS), 0, stream, acc, W);
-        LAUNCH_OK();
+        const RowJobs in = {{row_job(ROW_SHIFT, a.tar, Rb, rowsF, d0), row_job(ROW_SHIFT, a.tmask, tmb, rowsM, d0),
+                             row_job(ROW_OFFSET, var ? a.disparity : a.out, sh, rowsM, 0, (float)d0)}};
+        CK(decnet_launch(band_stage, dim3(row_grid(in)), dim3(EW_THREADS), 0, stream, in, W, 0));
+        band.tar = Rb;
+        band.tmask = tmb;
+        band.disparity = var ? sh : nullptr;
+        band.out = var ? a.out : sh;
+        band.grad_ref = glb;
+        band.grad_tar = grb;
+        band.grad_disp = var ? gdb : nullptr;
+        CK(decnet_mfma_backward(band));
+        const RowJobs acc = {{row_job(ROW_ADD, glb, a.grad_ref, rowsF, 0), row_job(ROW_ADD, grb, a.grad_tar, rowsF, d0),
+                              var ? row_job(ROW_ADD, gdb, a.grad_disp, rowsM, 0) : RowJob{}}};
+        CK(decnet_launch(band_accumulate, dim3(row_grid(acc)), dim3(EW_THREADS), 0, stream, acc, W));
     }
     return 0;
 }

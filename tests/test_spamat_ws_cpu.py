@@ -1,7 +1,8 @@
 """The caller-workspace SpaMat / SpaVar entries (decnet_spamat_workspace_floats and the six `_ws` entries of
 include/decnet_hip.h) as far as they go without a GPU: the symbols exist in the header, the library and the ctypes table;
 the size query is a pure host function with the values the header states; every `_ws` entry rejects null pointers, bad
-shapes and a missing / short / misaligned workspace before any HIP call."""
+shapes and a missing / short / misaligned workspace before any HIP call, and the six legacy entries (the same pointer
+counts, no workspace arguments) reject null pointers and bad shapes the same way."""
 import ctypes
 import os
 import re
@@ -21,6 +22,7 @@ ENTRIES = {
     "decnet_spamat_backward_ws": (10, 4),
     "decnet_spavar_backward_ws": (12, 5),
 }
+LEGACY = {name[:-3]: v for name, v in ENTRIES.items()}          # the original entries: no workspace arguments
 SHAPES = [(1, 8, 2, 460), (2, 8, 3, 300), (1, 24, 5, 1000), (1, 8, 1, 100), (3, 1, 7, 273)]     # (B, C, H, W); some W < D
 WIDE = (274, 405, 621, 1089)
 ONE_BAND = (1, 64, 272, 273)
@@ -41,6 +43,9 @@ def lib():
     for name, (n, _) in ENTRIES.items():
         f = getattr(h, name)
         f.argtypes, f.restype = [P] * n + [I] * 5 + [P, Z, P], I
+    for name, (n, _) in LEGACY.items():
+        f = getattr(h, name)
+        f.argtypes, f.restype = [P] * n + [I] * 5 + [P], I
     return h
 
 
@@ -84,13 +89,19 @@ def test_query_above_one_band_is_positive_and_within_what_the_library_allocated_
             assert n == [(C + 4) * np_, (C + 5) * np_, (C + 5) * np_, (C + 6) * np_, (3 * C + 2) * np_, (3 * C + 3) * np_]
 
 
-@pytest.mark.parametrize("name", list(ENTRIES))
+@pytest.mark.parametrize("name", list(ENTRIES) + list(LEGACY))
 def test_ws_entry_validates_before_any_hip_call(lib, name):
-    """No device is needed (or present): every rejection happens on the host.  Pointers are small fake addresses."""
-    f = getattr(lib, name)
+    """No device is needed (or present): every rejection happens on the host.  Pointers are small fake addresses.
+    The legacy entries take the same tensor pointers and dims, then the stream alone."""
+    entry = getattr(lib, name)
     q = getattr(lib, QUERY)
-    n, which = ENTRIES[name]
+    has_ws = name in ENTRIES
+    n, which = ENTRIES[name] if has_ws else LEGACY[name]
     one = 64                                                     # a fake, 16-byte aligned, never dereferenced address
+
+    def f(*a):                                                   # a: pointers, dims, workspace, floats, stream
+        return entry(*a) if has_ws else entry(*a[:-3], a[-1])
+
     ptrs = [one] * n
     ok = (1, 8, 2, 460)
     # null pointers: every tensor argument in turn, at one band and above
@@ -103,6 +114,15 @@ def test_ws_entry_validates_before_any_hip_call(lib, name):
     for dims in ((0, 8, 2, 460, 405), (1, 0, 2, 460, 405), (1, 8, 0, 460, 405), (1, 8, 2, 0, 405), (1, 8, 2, 460, 0),
                  (1, 8, 2, 460, -1), (1, 8, 2, 0, 64)):
         assert f(*ptrs, *dims, one, 1 << 40, None) == -2, (name, dims)
+    # a null tensor pointer wins over a bad shape
+    a = list(ptrs)
+    a[0] = None
+    assert f(*a, 1, 8, 2, 0, 405, one, 1 << 40, None) == -1
+    a = list(ptrs)
+    a[n - 1] = None
+    assert f(*a, 0, 8, 2, 460, 64, one, 1 << 40, None) == -1
+    if not has_ws:
+        return
     # the workspace contract at max_disp 405
     need = q(*ok, 405, which)
     assert need > 0
