@@ -65,6 +65,8 @@ SIGNATURES = {
     "decnet_conv2d_cat_epilogue": [_P, _P, _I, _P, _P, _P, _P] + [_I] * 7 + [_P, _P, _P],
     "decnet_conv2d_wgrad_workspace_floats": [_I] * 6,
     "decnet_conv2d_wgrad": [_P, _P, _I] + [_P] * 6 + [_Z] + [_I] * 6 + [_P],
+    "decnet_conv2d_mfma_wgrad_workspace_floats": [_I] * 6,
+    "decnet_conv2d_mfma_wgrad": [_P, _P, _I] + [_P] * 6 + [_Z] + [_I] * 6 + [_P],
     "decnet_conv2d_mfma_packed_bytes": [_I] * 3,
     "decnet_conv2d_mfma_pack_weight": [_P, _P] + [_I] * 3 + [_P],
     "decnet_conv2d_mfma_cat_bn_act": [_P, _P, _I, _P, _P, _P, _P] + [_I] * 7 + [_P],

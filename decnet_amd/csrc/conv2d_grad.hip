@@ -18,6 +18,7 @@
 // thread (element, s) the sets s, s + 16, ... in rising order, then the 16 sums in rising s -- and rounds once to fp32.
 // No atomics.  The longest fp32 addition chain is one accumulator's MFMA K chain: 64 pixels x RB rows = 512 terms.
 #include "common.h"
+#include "conv2d_wgrad_reduce.h"
 
 typedef int i32x4_g __attribute__((ext_vector_type(4)));
 typedef float f32x4_g __attribute__((ext_vector_type(4)));
@@ -164,26 +165,6 @@ __global__ __launch_bounds__(256) void conv2d_wgrad_partial(Segs in, const float
                 const int co = mt * 16 + 4 * kq + e, n = 16 * j + m;
                 if (co < Cout && n < N1) wp[(size_t)co * N1 + n] = acc[mt][j][e];
             }
-}
-
-// G[co][n] (n < N) and gsum[co] (n = N) = the float64 sum of the `nsets` partial sets, rounded once.
-__global__ __launch_bounds__(256) void conv2d_wgrad_reduce(const float *__restrict__ ws, float *__restrict__ G,
-                                                           float *__restrict__ gsum, int nsets, int Cout, int N1) {
-    __shared__ double part[16][17];
-    const int e = threadIdx.x & 15, s = threadIdx.x >> 4;
-    const int total = Cout * N1, el = blockIdx.x * 16 + e;
-    double a = 0.0;
-    if (el < total)
-        for (int set = s; set < nsets; set += 16) a += (double)ws[(size_t)set * total + el];
-    part[s][e] = a;
-    __syncthreads();
-    if (s == 0 && el < total) {
-        double t = 0.0;
-        for (int i = 0; i < 16; ++i) t += part[i][e];
-        const int co = el / N1, n = el - co * N1;
-        if (n == N1 - 1) gsum[co] = (float)t;
-        else G[(size_t)co * (N1 - 1) + n] = (float)t;
-    }
 }
 
 // the shapes the kernels cover -> number of workgroups of the first launch (0: not covered)

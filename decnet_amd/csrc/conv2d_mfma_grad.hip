@@ -1,0 +1,266 @@
+// decnet_amd/csrc/conv2d_mfma_grad.hip -- the weight-gradient reduction of the many-channel stride-1 Conv2dUnit layers
+// (csrc/conv2d_mfma.hip, Unit._route "mfma") with frozen BatchNorm.  The meaning is that of csrc/conv2d_grad.hip:
+//     gm                = gy * [y > 0]                                                         (gy itself without y)
+//     G[co][ci][ky][kx] = sum_{b,y,x} gm[b][co][y][x] * x[b][ci][y + (ky - k/2) d][x + (kx - k/2) d]     (zeros outside)
+//     gsum[co]          = sum_{b,y,x} gm[b][co][y][x]
+// for Cout, Cin <= 224, where G (up to 224 x 2017 with the column of ones that yields gsum) no longer fits one wave.
+//
+// Three launches, all on the caller's stream:
+//   1. conv2d_relu_mask forms gm once (skipped when gm is NULL: no ReLU, gm is gy);
+//   2. conv2d_mfma_wgrad_partial runs the GEMM [Cout x pixels] . [pixels x (Cin k k + 1)] on v_mfma_f32_16x16x4_f32 (bit
+//      for bit an fp32 fma chain over the pixels).  A 256-thread workgroup owns every row of G (MT tiles of 16 channels),
+//      one block of 64 NT GEMM columns (wave w the tiles w NT .. w NT + NT - 1: 4 MT NT accumulator registers) and one
+//      slice of `sl` consecutive chunks of one image; a chunk is 64 consecutive pixels of the plane, rows run on.  Per
+//      chunk the workgroup stages gm as [co][px] and the tap planes as [n][px] in LDS (pitch 68: the 16-byte operand
+//      reads of 16 lanes hit 64 different banks), wave w the rows w, w + 4, ..., lane = pixel: every load is one coalesced dword per lane, issued
+//      unconditionally from an address clamped into the plane and selected afterwards, at any float alignment.  The loads
+//      of chunk c + 1 are in flight while the MFMAs of chunk c run.  The tap rows' plane pointers and offsets sit in the
+//      registers of the wave's lanes and are handed out by v_readlane.
+//   3. conv2d_wgrad_reduce (csrc/conv2d_wgrad_reduce.h) adds the partial sets in a fixed order in float64 and rounds once.
+// LDS: (16 MT + 64 NT) rows x 272 bytes; NT = 2 up to MT = 6 (60 928 bytes), NT = 1 above (MT = 14: 78 336 bytes), so two
+// workgroups fit the 160 KiB of a CU; __launch_bounds__(256, 2) keeps the registers to that too.
+// Partition and order are functions of the shape alone (plan() below): workgroup v = (b, slice, column block), set
+// b nsl + slice, written to the caller's workspace [set][Cout][Cin k k + 1].  No atomics.  The longest fp32 addition chain
+// is one accumulator's MFMA K chain over its slice: 64 sl <= 4096 terms (sl = 64 chunks at most; halved down to 8 while
+// the launch has fewer than 512 workgroups).
+#include "common.h"
+#include "conv2d_wgrad_reduce.h"
+
+typedef float f32x4_w __attribute__((ext_vector_type(4)));
+
+namespace {
+
+constexpr int MAXSEG = 6;
+constexpr int MAXCH = 224;           // Cout and Cin
+constexpr int CP = 64;               // pixels of a chunk: 64 consecutive pixels of the plane, one per lane
+constexpr int PITCH = CP + 4;        // floats: rows 16-byte aligned, 16 rows x 4 quads hit 64 different banks
+constexpr int MAXSL = 64, MINSL = 8; // chunks of a slice: the fp32 chain is 64 sl terms
+struct Segs {
+    const float *p[MAXSEG];
+    int c[MAXSEG];
+    int n;
+};
+__global__ __launch_bounds__(256) void conv2d_relu_mask(const float *__restrict__ gy, const float *__restrict__ y,
+                                                        float *__restrict__ gm, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
+        gm[i] = !y || y[i] > 0.f ? gy[i] : 0.f;
+}
+
+// the float i of the global array at address `base`: a wave-uniform base and a 32-bit byte offset per lane (a plane is
+// below 2^29 floats)
+__device__ __forceinline__ float at(unsigned long long base, int i) {
+    return *reinterpret_cast<const __attribute__((address_space(1))) float *>(base + ((unsigned)i << 2));
+}
+
+template <int MT, int NT>
+__global__ __launch_bounds__(256, 2) void conv2d_mfma_wgrad_partial(Segs in, const float *__restrict__ gm,
+                                                                    float *__restrict__ ws, int Cout, int cin, int H, int W,
+                                                                    int k, int dil, int ncb, int nsl, int sl) {
+    constexpr int AR = MT * 4, BR = NT * 16;                             // rows a wave stages per chunk
+    constexpr int MG = MT > 9 ? 5 : MT;
+    __shared__ __attribute__((aligned(16))) float At[MT * 16 * PITCH];   // gm [co][px]; rows co >= Cout hold zeros
+    __shared__ __attribute__((aligned(16))) float Bt[NT * 64 * PITCH];   // the taps [n][px] of the column block
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int m = lane & 15, kq = lane >> 4;
+    const int v = blockIdx.x, cb = v % ncb, vs = v / ncb, s = vs % nsl, b = vs / nsl;
+    const int HW = H * W, c0 = s * sl, c1 = min((HW + CP - 1) / CP, c0 + sl);
+    const int kk = k * k, N = cin * kk, h = k / 2;                      // GEMM column N: the ones of gsum
+    const size_t plane = (size_t)HW;
+    // The tap rows this wave stages, wave + 4 i of the block (i < BR), live in the registers of lane i: the plane of (b, ci),
+    // the tap's distance off = dy W + dx in the plane, and tp = 3 ky + kx (k = 1: 0), 9 for the column of ones, 10 for a
+    // column past the GEMM.  v_readlane hands them out as scalars: no table in memory, no load that waits for one.
+    const float *r_p = in.p[0] + (size_t)b * in.c[0] * plane;
+    int r_off = 0, r_tp = 10;
+    const int dyc = min(dil, H), dxc = min(dil, W);                     // (a tap a whole image away never meets the image)
+    {
+        const int n = cb * (NT * 64) + wave + 4 * min(lane, BR - 1);
+        if (n == N) r_tp = 9;
+        if (n < N) {
+            const int ci = n / kk, tp = n - ci * kk, ky = tp / k, kx = tp - ky * k;
+            int sg = 0, cs = ci;
+            while (cs >= in.c[sg]) cs -= in.c[sg++];
+            r_p = in.p[sg] + ((size_t)b * in.c[sg] + cs) * plane;
+            r_off = (ky - h) * dyc * W + (kx - h) * dxc;                // (used only where the tap meets the image)
+            r_tp = k == 1 ? 0 : tp;
+        }
+    }
+    const int r_lo = (int)(unsigned long long)r_p, r_hi = (int)((unsigned long long)r_p >> 32);
+    const float *ga = gm + (size_t)b * Cout * plane;
+    // The loads of chunk c: wave w the rows w, w + 4, ... of both tiles, lane the pixel 64 c + lane of the plane.  Every
+    // load is issued from an address inside its plane; what it is worth (okb: the tap meets the image, inp: the pixel
+    // exists) is applied when the value goes to LDS, so that no load waits for the one before it.
+    float pre[AR + BR];
+    unsigned okb = 0;
+    bool inp = false;
+    auto load = [&](int c) {
+        const int p = c * CP + lane, pc = min(p, HW - 1), yy = pc / W, x = pc - yy * W;
+        inp = p < HW;
+        unsigned tapok = inp;                                           // bit 3 ky + kx: that tap of this pixel is in the image
+        if (k == 3) {
+            tapok = 0;
+#pragma unroll
+            for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+                for (int kx = 0; kx < 3; ++kx)
+                    tapok |= (unsigned)(inp & ((unsigned)(yy + (ky - 1) * dyc) < (unsigned)H) &
+                                        ((unsigned)(x + (kx - 1) * dxc) < (unsigned)W)) << (3 * ky + kx);
+        }
+        okb = 0;
+#pragma unroll
+        for (int i = 0; i < AR; ++i) pre[i] = at((unsigned long long)(ga + (size_t)min(wave + 4 * i, Cout - 1) * plane), pc);
+#pragma unroll
+        for (int i = 0; i < BR; ++i) {
+            const unsigned long long base = (unsigned long long)(unsigned)__builtin_amdgcn_readlane(r_lo, i) |
+                                            (unsigned long long)(unsigned)__builtin_amdgcn_readlane(r_hi, i) << 32;
+            const unsigned ok = tapok >> __builtin_amdgcn_readlane(r_tp, i) & 1;
+            pre[AR + i] = at(base, pc + (__builtin_amdgcn_readlane(r_off, i) & -(int)ok));
+            okb |= ok << i;
+        }
+    };
+    f32x4_w acc[MT][NT];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int j = 0; j < NT; ++j) acc[mt][j] = f32x4_w{0.f, 0.f, 0.f, 0.f};
+    load(c0);
+    for (int c = c0; c < c1; ++c) {
+#pragma unroll
+        for (int i = 0; i < AR; ++i) At[(wave + 4 * i) * PITCH + lane] = inp && wave + 4 * i < Cout ? pre[i] : 0.f;
+#pragma unroll
+        for (int i = 0; i < BR; ++i) {
+            const float other = __builtin_amdgcn_readlane(r_tp, i) == 9 ? 1.f : 0.f;     // (the column of ones)
+            Bt[(wave + 4 * i) * PITCH + lane] = okb >> i & 1 ? pre[AR + i] : other;
+        }
+        __syncthreads();
+        load(min(c + 1, c1 - 1));
+        // ---- four groups of 16 pixels, lane (m, kq) the pixels 16 g + 4 kq + e ----
+#pragma unroll
+        for (int gq = 0; gq < 4; ++gq) {
+            const int px = 16 * gq + 4 * kq;
+            f32x4_w b4[NT];
+#pragma unroll
+            for (int j = 0; j < NT; ++j)
+                b4[j] = *reinterpret_cast<const f32x4_w *>(&Bt[((wave * NT + j) * 16 + m) * PITCH + px]);
+#pragma unroll
+            for (int m0 = 0; m0 < MT; m0 += MG) {                       // (MG row tiles at a time: their operands in registers)
+                f32x4_w a4[MG];
+#pragma unroll
+                for (int mt = 0; mt < MG; ++mt)
+                    if (m0 + mt < MT) a4[mt] = *reinterpret_cast<const f32x4_w *>(&At[((m0 + mt) * 16 + m) * PITCH + px]);
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+#pragma unroll
+                    for (int mt = 0; mt < MG; ++mt)
+#pragma unroll
+                        for (int j = 0; j < NT; ++j)
+                            if (m0 + mt < MT)
+                                acc[m0 + mt][j] =
+                                    __builtin_amdgcn_mfma_f32_16x16x4f32(a4[mt][e], b4[j][e], acc[m0 + mt][j], 0, 0, 0);
+            }
+        }
+        __syncthreads();
+    }
+    // D: register e of lane (m, kq) is row 4 kq + e (channel), column m (GEMM column)
+    const int N1 = N + 1;
+    float *wp = ws + ((size_t)b * nsl + s) * ((size_t)Cout * N1);
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int j = 0; j < NT; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int co = mt * 16 + 4 * kq + e, n = ((cb * 4 + wave) * NT + j) * 16 + m;
+                if (co < Cout && n < N1) wp[(size_t)co * N1 + n] = acc[mt][j][e];
+            }
+}
+
+// the partition of a shape (sets == 0: not covered)
+struct Plan {
+    int mt, nt, ncb, nsl, sl;
+    long sets, groups;
+};
+
+Plan plan(int B, int Cin, int Cout, int H, int W, int k) {
+    Plan p{};
+    if (B < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1) return p;
+    if ((k != 1 && k != 3) || Cout > MAXCH || Cin > MAXCH || H > 65535 || B > 65535) return p;
+    if ((double)H * W >= 536870912.0 || (double)B * (Cin > Cout ? Cin : Cout) * H * W >= 9.0e18) return p;
+    const int tiles = ceil_div(Cout, 16), N1 = Cin * k * k + 1;
+    p.mt = tiles <= 3 ? tiles : tiles <= 5 ? 5 : tiles <= 6 ? 6 : tiles <= 9 ? 9 : 14;
+    p.nt = p.mt <= 6 && N1 > 64 ? 2 : 1;
+    p.ncb = ceil_div(N1, 64 * p.nt);
+    const long C = ((long)H * W + CP - 1) / CP;                        // chunks of one image
+    p.sl = MAXSL;
+    while (p.sl > MINSL && (double)B * ((C + p.sl - 1) / p.sl) * p.ncb < 512.0) p.sl >>= 1;
+    const long nsl = (C + p.sl - 1) / p.sl;
+    if ((double)B * nsl * p.ncb >= 2.0e9 || (double)B * nsl >= 2.0e9) return p;   // (workgroups and sets are ints)
+    p.nsl = (int)nsl;
+    p.sets = (long)B * nsl;
+    p.groups = p.sets * p.ncb;
+    return p;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t decnet_conv2d_mfma_wgrad_workspace_floats(int B, int Cin, int Cout, int H, int W, int k) {
+    const Plan p = plan(B, Cin, Cout, H, W, k);
+    if (p.sets == 0) return 0;
+    const size_t n = (size_t)p.sets * Cout * ((size_t)Cin * k * k + 1);
+    return (n + 3) & ~(size_t)3;
+}
+
+int decnet_conv2d_mfma_wgrad(const float *const *xs, const int *cins, int nseg, const float *gy, const float *y, float *gm,
+                             float *G, float *gsum, float *workspace, size_t workspace_floats, int B, int Cout, int H,
+                             int W, int k, int dilation, void *stream) {
+    if (!xs || !cins || !gy || !G || !gsum || !workspace || (y && !gm)) return DECNET_ERR_NULL_POINTER;
+    if (nseg < 1 || nseg > MAXSEG) return DECNET_ERR_UNSUPPORTED;
+    if (B < 1 || Cout < 1 || H < 1 || W < 1 || dilation < 1) return DECNET_ERR_BAD_SHAPE;
+    Segs in{};
+    int cin = 0;
+    for (int i = 0; i < nseg; ++i) {
+        if (!xs[i]) return DECNET_ERR_NULL_POINTER;
+        if (cins[i] < 1) return DECNET_ERR_BAD_SHAPE;
+        if (cins[i] > MAXCH) return DECNET_ERR_UNSUPPORTED;
+        in.p[i] = xs[i]; in.c[i] = cins[i];
+        cin += cins[i];
+    }
+    in.n = nseg;
+    if ((k != 1 && k != 3) || Cout > MAXCH || cin > MAXCH) return DECNET_ERR_UNSUPPORTED;
+    if ((double)B * (cin > Cout ? cin : Cout) * H * W >= 9.0e18) return DECNET_ERR_BAD_SHAPE;
+    const Plan p = plan(B, cin, Cout, H, W, k);
+    if (p.sets == 0) return DECNET_ERR_UNSUPPORTED;
+    if (workspace_floats < decnet_conv2d_mfma_wgrad_workspace_floats(B, cin, Cout, H, W, k)) return DECNET_ERR_BAD_SHAPE;
+    if ((uintptr_t)workspace & 15) return DECNET_ERR_MISALIGNED;
+    hipStream_t s = (hipStream_t)stream;
+    int rc;
+    if (gm) {                                                         // (without y: a copy, as decnet_conv2d_wgrad)
+        const size_t n = (size_t)B * Cout * H * W, blocks = (n + 1023) / 1024;
+        hipLaunchKernelGGL(conv2d_relu_mask, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, s, gy, y, gm, n);
+        if ((rc = decnet_launch_status())) return rc;
+    }
+    const float *a = y ? gm : gy;
+    const dim3 grid((unsigned)p.groups);
+#define GO(MT_, NT_)                                                                                                  \
+    hipLaunchKernelGGL((conv2d_mfma_wgrad_partial<MT_, NT_>), grid, dim3(256), 0, s, in, a, workspace, Cout, cin, H, W, \
+                       k, dilation, p.ncb, p.nsl, p.sl)
+#define GON(MT_)                                                                                                      \
+    case MT_:                                                                                                         \
+        if (p.nt == 2) GO(MT_, 2); else GO(MT_, 1);                                                                   \
+        break
+    switch (p.mt) {
+        GON(1); GON(2); GON(3); GON(5); GON(6);
+        case 9: GO(9, 1); break;
+        default: GO(14, 1);
+    }
+#undef GON
+#undef GO
+    if ((rc = decnet_launch_status())) return rc;
+    const int N1 = cin * k * k + 1;
+    hipLaunchKernelGGL(conv2d_wgrad_reduce, dim3((unsigned)ceil_div(Cout * N1, 16)), dim3(256), 0, s, workspace, G, gsum,
+                       (int)p.sets, Cout, N1);
+    return decnet_launch_status();
+}
+
+}  // extern "C"

@@ -21,7 +21,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops2d
-from .conv2d_grad import Conv2dSmallFunction, hip_grad_enabled
+from .conv2d_grad import Conv2dMfmaFunction, Conv2dSmallFunction, hip_grad_enabled
 from .tail_grad import DynamicUpsample3Function, SigmoidBlendFunction, Unfold3CatFunction, WarpDisparityFunction
 from ._lib import DecnetHipError, UNSUPPORTED
 from .ops import spamatvar_forward, spamatvar_forward_bits
@@ -94,6 +94,23 @@ def tail_grad_route(op, B, C, H, W, s=3, fea_hw=None):
     if op == "upsample":
         return s == 3 and H <= 65535
     raise ValueError("no such op: %s" % op)
+
+
+def _mfma_grad_slower(cin, cout, hw):
+    """The "mfma" shapes that stay on the library under ``hip_grad()``: those whose forward + backward was measured slower
+    than (or level with) the library's under autograd -- eager, B = 4, one run (tools/bench_conv2d_mfma_grad.py,
+    profiles/conv2d_mfma_grad.json).  Only two sizes were measured, the model's levels 60 x 108 (6480 pixels) and
+    180 x 324 (58320 pixels); the rule looks at channels and pixels, not at B.
+      * At 6480 pixels every unit was slower (72 -> 72, 144 -> 72, 217 -> 81, 81 -> 81, 76 -> 8: 0.52 - 0.98 of the
+        library's speed eager, 0.65 - 1.00 as GraphedStep replays).  That verdict is carried up to the next measured size,
+        58320 pixels, where units were first measured faster; nothing between the two was measured.
+      * At 58320 pixels the units with at most 24 inputs and 24 outputs were slower eager (24 -> 24: 0.74 with k 3, 0.63
+        with k 1) although faster as replays (1.42, 1.90): an eager step of one unit is some 25 small launches and is bound
+        by the host.  They stay on the library from 6480 pixels on; the wider units there are 1.30 - 1.32 x the library.
+    Below 6480 pixels nothing is excluded: the route's floor is the forward's (4096 pixels), where the tests of the Function
+    run.  No layer of the model has such a shape at config 5; measured at 1 x 64 x 64, 24 -> 24 and 73 -> 81 are 0.54 and
+    0.56 of the library's speed (0.51 and 0.43 as replays), so a caller with images that small gains nothing there."""
+    return hw >= 6480 and (hw < 58320 or (cin <= 24 and cout <= 24))
 
 
 def _same_padded(c):
@@ -188,6 +205,18 @@ class Unit(CachesWeights, nn.Module):
             return None
         return "conv" if self._route(B, H, W, parts, switches=(True, True)) == "conv" else None
 
+    def _grad_route_mfma(self, B, H, W, parts=None):
+        """"mfma" when the unit's backward runs on the HIP kernels under ``hip_grad()`` as conv2d_grad.Conv2dMfmaFunction,
+        else None: the layers _route sends to "mfma" with the switches at their defaults, within the channel limits of
+        decnet_conv2d_mfma_wgrad (224 inputs, 224 outputs), less the shapes measured slower than the library
+        (_mfma_grad_slower; tools/bench_conv2d_mfma_grad.py, profiles/conv2d_mfma_grad.json).  Pure, like _route."""
+        c = self.conv
+        if c.in_channels > 224 or c.out_channels > 224:
+            return None
+        if self._route(B, H, W, parts, switches=(True, True)) != "mfma":
+            return None
+        return None if _mfma_grad_slower(c.in_channels, c.out_channels, H * W) else "mfma"
+
     def _forward_grad(self, x):
         """The forward under ``hip_grad()`` with autograd on: the same kernels, the backward recorded on ours.  None
         where the unit, the input or the shape is not covered (the caller then goes on as it always did)."""
@@ -198,7 +227,10 @@ class Unit(CachesWeights, nn.Module):
                 t.shape[2:] != x0.shape[2:] for t in xs):
             return None
         parts = len(xs) if isinstance(x, (tuple, list)) else None
-        if self._grad_route(x0.shape[0], x0.shape[-2], x0.shape[-1], parts) is None:
+        route = self._grad_route(x0.shape[0], x0.shape[-2], x0.shape[-1], parts)
+        if route is None:
+            route = self._grad_route_mfma(x0.shape[0], x0.shape[-2], x0.shape[-1], parts)
+        if route is None:
             return None
         if self.bn is not None:                                         # differentiable (fold_bn's arithmetic)
             scale, shift = fold_bn(self.bn)
@@ -206,8 +238,11 @@ class Unit(CachesWeights, nn.Module):
             scale, shift = fold_none(c)
         n_tally = None if TALLY is None else len(TALLY)
         if TALLY is not None:
-            _tally(self, "conv_grad", x)
+            _tally(self, "conv_grad" if route == "conv" else "mfma_grad", x)
         try:
+            if route == "mfma":
+                return Conv2dMfmaFunction.apply(self._folded_mfma(), c.kernel_size[0], c.dilation[0], bool(self.relu),
+                                                c.weight, scale, shift, *xs)
             return Conv2dSmallFunction.apply(self._folded(), c.kernel_size[0], c.dilation[0], bool(self.relu), c.weight,
                                              scale, shift, *xs)
         except DecnetHipError as e:                     # the grid limits of the forward kernel: the library takes it

@@ -118,11 +118,9 @@ def conv2d_cat_epilogue(xs, w, scale, shift, cin, k, dil, relu, epi, ea, eb=None
 _WGRAD_FLOATS = {}
 
 
-def conv2d_wgrad(xs, gy, y, k, dil):
-    """Weight-gradient reduction of a few-channel stride-1 unit (decnet_conv2d_wgrad, csrc/conv2d_grad.hip): xs the parts
-    [B,c_i,H,W] of the input, gy [B,Cout,H,W], y the unit's output (the ReLU mask y > 0) or None -> (G [Cout,Cin,k,k],
-    gsum [Cout], gm = gy * [y > 0] [B,Cout,H,W]; gy itself without y).  The workspace comes from torch.empty, its size from
-    the library's query, cached per shape."""
+def _wgrad(name, xs, gy, y, k, dil):
+    """One weight-gradient entry `name` (decnet_conv2d_wgrad / decnet_conv2d_mfma_wgrad: one argument list).  The
+    workspace comes from torch.empty, its size from the library's query, cached per entry and shape."""
     B, Co, H, W = _chk("gy", gy).shape
     if y is not None:
         _chk("y", y, (B, Co, H, W))
@@ -131,21 +129,32 @@ def conv2d_wgrad(xs, gy, y, k, dil):
     cins, n = [int(t.shape[1]) for t in xs], len(xs)
     cin, k, dil = sum(cins), int(k), int(dil)
     key = (B, cin, Co, H, W, k)
-    nws = _WGRAD_FLOATS.get(key)
+    nws = _WGRAD_FLOATS.get((name,) + key)
     if nws is None:
-        nws = _WGRAD_FLOATS[key] = int(size("conv2d_wgrad_workspace_floats", *key))
+        nws = _WGRAD_FLOATS[(name,) + key] = int(size(name + "_workspace_floats", *key))
     if nws == 0:
-        raise _lib.DecnetHipError("decnet_conv2d_wgrad does not cover B %d, Cin %d, Cout %d, %d x %d, k %d"
-                                  % (B, cin, Co, H, W, k))
+        raise _lib.DecnetHipError("decnet_%s does not cover B %d, Cin %d, Cout %d, %d x %d, k %d" % ((name,) + key))
     dev = gy.device
     G = torch.empty((Co, cin, k, k), dtype=_F32, device=dev)
     gsum = torch.empty((Co,), dtype=_F32, device=dev)
     gm = gy if y is None else torch.empty_like(gy)
     ws = torch.empty(nws, dtype=_F32, device=dev)                      # torch allocations are 16-byte aligned
-    _call("decnet_conv2d_wgrad", gy, (ctypes.c_void_p * n)(*[t.data_ptr() for t in xs]), (ctypes.c_int * n)(*cins), n,
+    _call("decnet_" + name, gy, (ctypes.c_void_p * n)(*[t.data_ptr() for t in xs]), (ctypes.c_int * n)(*cins), n,
           gy.data_ptr(), None if y is None else y.data_ptr(), None if y is None else gm.data_ptr(), G.data_ptr(),
           gsum.data_ptr(), ws.data_ptr(), nws, B, Co, H, W, k, dil)
     return G, gsum, gm
+
+
+def conv2d_wgrad(xs, gy, y, k, dil):
+    """Weight-gradient reduction of a few-channel stride-1 unit (decnet_conv2d_wgrad, csrc/conv2d_grad.hip): xs the parts
+    [B,c_i,H,W] of the input, gy [B,Cout,H,W], y the unit's output (the ReLU mask y > 0) or None -> (G [Cout,Cin,k,k],
+    gsum [Cout], gm = gy * [y > 0] [B,Cout,H,W]; gy itself without y)."""
+    return _wgrad("conv2d_wgrad", xs, gy, y, k, dil)
+
+
+def conv2d_mfma_wgrad(xs, gy, y, k, dil):
+    """The same reduction for a many-channel unit (decnet_conv2d_mfma_wgrad, csrc/conv2d_mfma_grad.hip: Cin, Cout <= 224)."""
+    return _wgrad("conv2d_mfma_wgrad", xs, gy, y, k, dil)
 
 
 def bias_act_inplace(x, b, relu):

@@ -402,6 +402,25 @@ size_t decnet_conv2d_wgrad_workspace_floats(int B, int Cin, int Cout, int H, int
 int decnet_conv2d_wgrad(const float *const *xs, const int *cins, int nseg, const float *gy, const float *y, float *gm,
                         float *G, float *gsum, float *workspace, size_t workspace_floats, int B, int Cout, int H,
                         int W, int k, int dilation, void *stream);
+/* Weight gradient of decnet_conv2d_mfma_cat_bn_act with frozen BatchNorm (csrc/conv2d_mfma_grad.hip): the meaning of
+ * decnet_conv2d_wgrad, argument for argument, for the many-channel layers -- gm = gy * [y > 0] (written in full; y NULL:
+ * no ReLU, gm may be NULL and is gy), G[co][ci][ky][kx] = sum gm * x(tap) with zeros outside the image at any
+ * dilation >= 1, gsum[co] = sum gm; G and gsum written in full.  dx is decnet_conv2d_mfma_cat_bn_act itself on gm with
+ * the weights w'[ci][co][ky][kx] = w[co][ci][k-1-ky][k-1-kx] * scale[co].
+ *   xs, cins, nseg   the input as for decnet_conv2d_mfma_cat_bn_act (nseg <= 6, Cin = sum of cins <= 224, any split)
+ *   Cout             <= 224; k 1 or 3; B, H <= 65535; H * W < 2^29 (a plane is addressed by a 32-bit byte offset)
+ *   workspace        decnet_conv2d_mfma_wgrad_workspace_floats(B, Cin, Cout, H, W, k) floats (0: shape not covered),
+ *                    16-byte aligned (else DECNET_ERR_MISALIGNED); fewer floats than the query: DECNET_ERR_BAD_SHAPE
+ * Every other buffer is accepted at any float alignment, W at any value.  The GEMM [Cout x pixels] . [pixels x (Cin k k + 1)]
+ * runs on v_mfma_f32_16x16x4_f32 (an fp32 fma chain; no bf16 split).  Deterministic: partition and order are functions of
+ * the shape alone; workgroups write partial sums (fp32 chains of at most 4096 terms: 64 pixels x at most 64 chunks) into
+ * the workspace, a last launch adds them in a fixed order in float64 and rounds once; no atomics, no allocation, no
+ * synchronisation (capturable).  NULL (also y without gm): DECNET_ERR_NULL_POINTER; k not 1 or 3, Cout > 224, Cin > 224,
+ * nseg > 6, H or B > 65535, H * W >= 2^29: DECNET_ERR_UNSUPPORTED.  Nothing is launched on any refusal. */
+size_t decnet_conv2d_mfma_wgrad_workspace_floats(int B, int Cin, int Cout, int H, int W, int k);
+int decnet_conv2d_mfma_wgrad(const float *const *xs, const int *cins, int nseg, const float *gy, const float *y,
+                             float *gm, float *G, float *gsum, float *workspace, size_t workspace_floats, int B, int Cout,
+                             int H, int W, int k, int dilation, void *stream);
 /* Refinement.get_warped_feats_by_homgrp (submodule.py:719-745): out[b,c,y,x] = bilinear(right[b,c];
  * (x - disp[b,y,x]) * W/(W-1) - 0.5, y * H/(H-1) - 0.5), zero padding.  right,out [B,C,H,W], disp [B,H,W]. */
 int decnet_warp_disparity(const float *right, const float *disp, float *out, int B, int C, int H, int W,
