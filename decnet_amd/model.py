@@ -363,6 +363,20 @@ class Unit(CachesWeights, nn.Module):
                 return ops2d.bias_act_inplace(x, b, 1 if self.relu else 0)
             x = x + b.view(1, -1, 1, 1)
             return torch.relu_(x) if self.relu else x
+        if self.bn is not None and not self.training and x.is_cuda and hip_grad_enabled() and torch.is_grad_enabled():
+            # a unit that stays on the library under hip_grad(): the arithmetic of the no_grad route above (BatchNorm folded
+            # into the weights, then bias and ReLU), as differentiable torch ops -- the forward keeps the inference
+            # forward's bits, like the units on the HIP Functions beside it
+            scale, shift = fold_bn(self.bn, fp32=False)
+            c = self.conv
+            if isinstance(c, nn.ConvTranspose2d):
+                x = F.conv_transpose2d(x, (c.weight * scale.view(1, -1, 1, 1)).contiguous(), None, c.stride, c.padding,
+                                       c.output_padding, c.groups, c.dilation)
+            else:
+                x = F.conv2d(x, (c.weight * scale.view(-1, 1, 1, 1)).contiguous(), None, c.stride, c.padding, c.dilation,
+                             c.groups)
+            x = x + shift.view(1, -1, 1, 1)
+            return torch.relu(x) if self.relu else x
         x = self.conv(x)
         if self.bn is not None:
             x = self.bn(x)

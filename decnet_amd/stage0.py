@@ -17,6 +17,7 @@ import os
 
 import torch
 import torch.nn as nn
+from torch.optim.optimizer import register_optimizer_step_post_hook
 
 from . import _lib, ops2d
 from .ops import _chk
@@ -27,12 +28,29 @@ BN_EPS = 1e-5
 WINO_VARIANT = {"winograd": 0, "winograd4": 1, "winograd444": 2}
 
 
+# Optimizer steps taken in this process.  The fused optimizers (``torch.optim.Adam(fused=True)``, ``SGD(fused=True)``, ...)
+# update the parameters in one kernel that leaves ``_version`` alone, so a key of addresses and versions would keep the
+# packed weights of the step before: the forward under ``hip_grad()`` on last step's weights, the backward (which reads
+# the live ``conv.weight``) on this step's.  A global post-step hook counts the steps, and the count is part of every key:
+# after any ``optimizer.step()`` every cache repacks on its next use (a pack kernel per layer and step).
+_OPTIMIZER_STEPS = [0]
+
+
+def _count_optimizer_step(optimizer, args, kwargs):
+    _OPTIMIZER_STEPS[0] += 1
+
+
+register_optimizer_step_post_hook(_count_optimizer_step)
+
+
 def source_key(ts, *extra):
-    """Key of a packed-weight cache: (address, version) of every tensor it is built from, plus the plain values that go
-    into the packing.  It sees in-place writes under ``no_grad``, ``load_state_dict`` and a re-assigned ``.data`` at a new
-    address; it cannot see a write THROUGH ``.data`` (``p.data.copy_()``, ``p.data.normal_()``), which changes neither
-    -- such writes after the first forward need ``decnet_amd.drop_weight_caches(model)``."""
-    return tuple((t.data_ptr(), t._version) for t in ts) + tuple(extra)
+    """Key of a packed-weight cache: (address, version, optimizer steps so far) of every tensor it is built from, plus the
+    plain values that go into the packing.  It sees in-place writes under ``no_grad``, ``load_state_dict``, a re-assigned
+    ``.data`` at a new address and every ``optimizer.step()`` (the fused ones do not bump the version); it cannot see a
+    write THROUGH ``.data`` (``p.data.copy_()``, ``p.data.normal_()``), which changes none of them -- such writes after
+    the first forward need ``decnet_amd.drop_weight_caches(model)``."""
+    steps = _OPTIMIZER_STEPS[0]
+    return tuple((t.data_ptr(), t._version, steps) for t in ts) + tuple(extra)
 
 
 def source_hold(ts):
