@@ -60,6 +60,8 @@ SIGNATURES = {
     "decnet_sigmoid_blend": [_P] * 4 + [_Z, _P],
     "decnet_sigmoid_blend_backward": [_P] * 7 + [_Z, _P],
     "decnet_s2d3_pad1": [_P, _P] + [_I] * 4 + [_P],
+    "decnet_d2s3_pad1": [_P, _P] + [_I] * 4 + [_P],
+    "decnet_s2d3_pad0": [_P, _P] + [_I] * 4 + [_P],
     "decnet_detail_mask": [_P] * 6 + [_F] * 3 + [_P] * 3 + [_I] * 3 + [_P],
     "decnet_conv2d_cat_bn_act": [_P, _P, _I, _P, _P, _P, _P] + [_I] * 7 + [_P],
     "decnet_conv2d_cat_epilogue": [_P, _P, _I, _P, _P, _P, _P] + [_I] * 7 + [_P, _P, _P],
@@ -67,6 +69,10 @@ SIGNATURES = {
     "decnet_conv2d_wgrad": [_P, _P, _I] + [_P] * 6 + [_Z] + [_I] * 6 + [_P],
     "decnet_conv2d_mfma_wgrad_workspace_floats": [_I] * 6,
     "decnet_conv2d_mfma_wgrad": [_P, _P, _I] + [_P] * 6 + [_Z] + [_I] * 6 + [_P],
+    "decnet_conv2d_k3s3_wgrad_workspace_floats": [_I] * 5,
+    "decnet_conv2d_k3s3_wgrad": [_P] * 7 + [_Z] + [_I] * 5 + [_P],
+    "decnet_deconv2d_k3s3_wgrad_workspace_floats": [_I] * 5,
+    "decnet_deconv2d_k3s3_wgrad": [_P] * 7 + [_Z] + [_I] * 5 + [_P],
     "decnet_conv2d_mfma_packed_bytes": [_I] * 3,
     "decnet_conv2d_mfma_pack_weight": [_P, _P] + [_I] * 3 + [_P],
     "decnet_conv2d_mfma_cat_bn_act": [_P, _P, _I, _P, _P, _P, _P] + [_I] * 7 + [_P],

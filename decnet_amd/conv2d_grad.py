@@ -16,7 +16,16 @@ carries dscale / dshift on to ``bn.weight``, ``bn.bias`` and ``conv.bias``; noth
 same switch puts the warp, the dynamic upsampling and SoftAttention's blend on their HIP Functions (tail_grad.py).
 The many-channel stride-1 units of the matrix-core route (``Unit._route`` "mfma") take ``Conv2dMfmaFunction``: the same
 backward on decnet_conv2d_mfma_cat_bn_act and decnet_conv2d_mfma_wgrad (csrc/conv2d_mfma_grad.hip).
-Out of scope: training-mode BatchNorm, the stride-3 and transposed layers, stage 0, double backward.
+The layers between the pyramid levels -- Conv2d k 3, stride 3, padding 1 and ConvTranspose2d k 3, stride 3 (``Unit._route``
+"conv_s3", "mfma_s3", "deconv", "mfma_deconv") -- take ``Conv2dS3Function`` / ``Deconv2dS3Function``:
+
+    conv        G[co,ci,ky,kx] = sum gm[b,co,yo,xo] * x[b,ci,3yo-1+ky,3xo-1+kx]             decnet_conv2d_k3s3_wgrad
+                dx = d2s3_pad1(conv1x1(gm, (w * scale) read as [Cout, 9 Cin], transposed))   (every input pixel: one window)
+    transposed  G[ci,co,a,c] = sum x[b,ci,i,j] * gm[b,co,3i+a,3j+c]                          decnet_deconv2d_k3s3_wgrad
+                dx = conv1x1(s2d3_pad0(gm), (w * scale[co]) read as [Cin, 9 Cout])           (w [Cin,Cout,3,3], no flip)
+
+with the 1 x 1 convolutions on decnet_conv2d_mfma_cat_bn_act.
+Out of scope: training-mode BatchNorm, stage 0, the ASPP tap-conv block, the 20 x 36 stride-1 layers, double backward.
 """
 import contextlib
 import threading
@@ -56,29 +65,37 @@ def flipped_weight(w, scale, rows=None):
     return wt.contiguous()
 
 
-def _unit_backward(ctx, gy, wgrad, dx_conv):
-    """The backward of one unit, shared by the few-channel and the matrix-core Function.  wgrad(xs, gy, y, k, dil) ->
-    (G, gsum, gm): the weight-gradient entry; dx_conv(gm, wt, k, dil) -> conv(gm, wt) for wt [n, Cout, k, k]: the
-    forward entry on the flipped weights."""
+def _param_grads(ctx, gy, wgrad, co_dim=0, first=4):
+    """The parameter side of one unit's backward, shared by every Function here: -> (dw, dscale, dshift, gm, w32, s32).
+    wgrad(xs, gy, y) -> (G, gsum, gm): the weight-gradient entry, launched only when the weight or the scale wants a
+    gradient; co_dim: the output-channel axis of the weight (1 for a transposed layer); first: the position of w among the
+    Function's arguments (scale and shift follow it)."""
     w, scale, y = ctx.saved_tensors[:3]
-    xs = ctx.saved_tensors[3:]
-    need_w, need_scale, need_shift = ctx.needs_input_grad[4:7]
-    need_parts = ctx.needs_input_grad[7:]
-    gy = gy.contiguous()
+    need_w, need_scale, need_shift = ctx.needs_input_grad[first:first + 3]
     w32, s32 = w.detach().float().contiguous(), scale.detach().float()
+    sv = s32.view((-1, 1, 1, 1) if co_dim == 0 else (1, -1, 1, 1))
     dw = dscale = dshift = None
     if need_w or need_scale:
-        G, gsum, gm = wgrad(xs, gy, y, ctx.k, ctx.dil)
+        G, gsum, gm = wgrad(ctx.saved_tensors[3:], gy, y)
         if need_w:
-            dw = G * s32.view(-1, 1, 1, 1)
+            dw = G * sv
         if need_scale:
-            dscale = (w32.double() * G.double()).sum((1, 2, 3)).float()
+            dscale = (w32.double() * G.double()).sum((1, 2, 3) if co_dim == 0 else (0, 2, 3)).float()
         if need_shift:
             dshift = gsum
     else:                                   # no weight gradient wanted: the mask and the sum alone
         gm = gy if y is None else torch.ops.aten.threshold_backward(gy, y, 0)
         if need_shift:
             dshift = gm.sum((0, 2, 3), dtype=torch.float64).float()
+    return dw, dscale, dshift, gm, w32, s32
+
+
+def _unit_backward(ctx, gy, wgrad, dx_conv):
+    """The backward of one stride-1 unit, shared by the few-channel and the matrix-core Function.  wgrad(xs, gy, y, k,
+    dil) -> (G, gsum, gm): the weight-gradient entry; dx_conv(gm, wt, k, dil) -> conv(gm, wt) for wt [n, Cout, k, k]: the
+    forward entry on the flipped weights."""
+    need_parts = ctx.needs_input_grad[7:]
+    dw, dscale, dshift, gm, w32, s32 = _param_grads(ctx, gy.contiguous(), lambda xs, g, y: wgrad(xs, g, y, ctx.k, ctx.dil))
     grads = [None] * len(need_parts)
     if any(need_parts):
         rows, at, c0 = [], {}, 0
@@ -93,8 +110,8 @@ def _unit_backward(ctx, gy, wgrad, dx_conv):
     return (None, None, None, None, dw, dscale, dshift) + tuple(grads)
 
 
-def _save(ctx, k, dil, relu, w, scale, y, xs):
-    need_g = ctx.needs_input_grad[4] or ctx.needs_input_grad[5]
+def _save(ctx, k, dil, relu, w, scale, y, xs, first=4):
+    need_g = ctx.needs_input_grad[first] or ctx.needs_input_grad[first + 1]
     ctx.k, ctx.dil, ctx.relu, ctx.cins = k, dil, relu, [int(t.shape[1]) for t in xs]
     ctx.save_for_backward(w, scale, y if relu else None, *(xs if need_g else ()))
 
@@ -150,3 +167,64 @@ class Conv2dMfmaFunction(Function):
     @once_differentiable
     def backward(ctx, gy):
         return _unit_backward(ctx, gy, ops2d.conv2d_mfma_wgrad, _dx_mfma)
+
+
+def _conv1x1_mfma(x, wt):
+    """conv1x1(x, wt) for wt [n, C] on the matrix-core forward entry (scale 1, shift 0, no ReLU), packed per backward."""
+    n, c = wt.shape
+    return ops2d.conv2d_mfma_cat_bn_act([x], ops2d.conv2d_mfma_pack_weight(wt.contiguous(), c, 1),
+                                        torch.ones(n, device=x.device), torch.zeros(n, device=x.device), c, 1, 1, 0)
+
+
+class Conv2dS3Function(Function):
+    """apply(route, packed, relu, w, scale, shift, x) -> y [B,Cout,ceil(H/3),ceil(W/3)] for a Conv2d k 3, stride 3, padding 1
+    unit.  route: the unit's forward route, "conv_s3" (packed: ``Unit._folded()``) or "mfma_s3" (``Unit._folded_mfma()``):
+    the forward is that route's inference entry, so its bits are the ``no_grad`` forward's."""
+
+    @staticmethod
+    def forward(ctx, route, packed, relu, w, scale, shift, x):
+        x = x.contiguous()
+        ci = int(w.shape[1])
+        if route == "mfma_s3":
+            y = ops2d.conv2d_mfma_cat_bn_act([ops2d.s2d3_pad1(x)], *packed, 9 * ci, 1, 1, 1 if relu else 0)
+        else:
+            y = ops2d.conv2d_k3s3_bn_act(x, *packed, ci, 1 if relu else 0)
+        ctx.hw = (int(x.shape[2]), int(x.shape[3]))
+        _save(ctx, 3, 1, relu, w, scale, y, [x], first=3)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        dw, dscale, dshift, gm, w32, s32 = _param_grads(ctx, gy.contiguous(),
+                                                        lambda xs, g, y: ops2d.conv2d_k3s3_wgrad(xs[0], g, y), first=3)
+        dx = None
+        if ctx.needs_input_grad[6]:         # the 1 x 1 convolution Cout -> 9 Cin of gm, then the adjoint of s2d3_pad1
+            wt = (w32 * s32.view(-1, 1, 1, 1)).reshape(w32.shape[0], -1).t()
+            dx = ops2d.d2s3_pad1(_conv1x1_mfma(gm, wt), *ctx.hw)
+        return (None, None, None, dw, dscale, dshift, dx)
+
+
+class Deconv2dS3Function(Function):
+    """The same for a ConvTranspose2d k 3, stride 3 unit (w [Cin,Cout,3,3]; route "deconv" or "mfma_deconv") -> y
+    [B,Cout,3H,3W]."""
+
+    @staticmethod
+    def forward(ctx, route, packed, relu, w, scale, shift, x):
+        x = x.contiguous()
+        entry = ops2d.deconv2d_mfma_k3s3_bn_act if route == "mfma_deconv" else ops2d.deconv2d_k3s3_bn_act
+        y = entry(x, *packed, int(w.shape[0]), 1 if relu else 0)
+        _save(ctx, 3, 1, relu, w, scale, y, [x], first=3)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        dw, dscale, dshift, gm, w32, s32 = _param_grads(ctx, gy.contiguous(),
+                                                        lambda xs, g, y: ops2d.deconv2d_k3s3_wgrad(xs[0], g, y), co_dim=1,
+                                                        first=3)
+        dx = None
+        if ctx.needs_input_grad[6]:         # the space-to-depth of gm, then the 1 x 1 convolution 9 Cout -> Cin
+            wt = (w32 * s32.view(1, -1, 1, 1)).reshape(w32.shape[0], -1)
+            dx = _conv1x1_mfma(ops2d.s2d3_pad0(gm), wt)
+        return (None, None, None, dw, dscale, dshift, dx)

@@ -21,7 +21,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops2d
-from .conv2d_grad import Conv2dMfmaFunction, Conv2dSmallFunction, hip_grad_enabled
+from .conv2d_grad import Conv2dMfmaFunction, Conv2dS3Function, Conv2dSmallFunction, Deconv2dS3Function, hip_grad_enabled
 from .tail_grad import DynamicUpsample3Function, SigmoidBlendFunction, Unfold3CatFunction, WarpDisparityFunction
 from ._lib import DecnetHipError, UNSUPPORTED
 from .ops import spamatvar_forward, spamatvar_forward_bits
@@ -111,6 +111,29 @@ def _mfma_grad_slower(cin, cout, hw):
     run.  No layer of the model has such a shape at config 5; measured at 1 x 64 x 64, 24 -> 24 and 73 -> 81 are 0.54 and
     0.56 of the library's speed (0.51 and 0.43 as replays), so a caller with images that small gains nothing there."""
     return hw >= 6480 and (hw < 58320 or (cin <= 24 and cout <= 24))
+
+
+def _s3_grad_slower(route, cin, cout, n):
+    """The stride-3 shapes ("s3" / "deconv"; n = B H W, the pixels of the unit's INPUT over the batch) that stay on the
+    library under ``hip_grad()``: those whose forward + backward was measured slower than (or level with) the library's
+    under autograd -- eager, one run (tools/bench_conv2d_s3_grad.py, profiles/conv2d_s3_grad.json: the nine stride-3 units
+    of the model at config 5, B = 8 in the extractor, B = 4 in the mask generators; speed relative to the library eager,
+    in brackets as GraphedStep replays).
+      * "s3": conv1[0] (8 -> 24, n = 8 x 540 x 972, the few-channel forward) is 2.51 x the library (2.70) and stays.  The
+        units with more than 24 outputs (forward route "mfma_s3") were slower at both measured sizes -- conv3_1 72 -> 216 at
+        n = 8 x 6480 = 51840: 0.57 (0.79); conv2[0] 24 -> 72 at n = 8 x 58320: 0.61 (1.16) -- and go back to the library from
+        51840 pixels on.
+      * "deconv": with 72 or more inputs, slower from the smallest measured size up to the first one measured faster --
+        GenerateSparseMask(72).deconv[0] 216 -> 8 at n = 4 x 720 = 2880: 0.75 (0.70); deconv3.deconv 216 -> 72 at 5760: 0.64
+        (0.88); GenerateSparseMask(24).deconv[0] 72 -> 8 at 25920: 0.90 (0.89); then deconv2.deconv 72 -> 24 at 51840: 1.53
+        (1.56).  The 24-input units stay: deconv1.deconv 24 -> 8 at 8 x 58320: 6.57 (6.74), GenerateSparseMask(8).deconv[0]
+        at 4 x 58320: 1.57 (1.60).
+    Below the smallest measured n nothing is excluded (nothing was measured there): the routes' floors are the forwards',
+    where the tests of the Functions run.  An eager step of one unit is some 20 small launches and is bound by the host
+    at the small sizes, so a caller with one small image gains nothing there."""
+    if route == "s3":
+        return cout > 24 and n >= 51840
+    return cin >= 72 and 2880 <= n < 51840
 
 
 def _same_padded(c):
@@ -217,6 +240,21 @@ class Unit(CachesWeights, nn.Module):
             return None
         return None if _mfma_grad_slower(c.in_channels, c.out_channels, H * W) else "mfma"
 
+    def _grad_route_s3(self, B, H, W):
+        """"s3" / "deconv" when the unit's backward runs on the HIP kernels under ``hip_grad()`` as
+        conv2d_grad.Conv2dS3Function / Deconv2dS3Function, else None: the layers _route sends to "conv_s3" or "mfma_s3" /
+        to "deconv" or "mfma_deconv" with the switches at their defaults (so from those routes' floors on), within the
+        channel limits of the weight-gradient entries (224 inputs, 224 outputs), less the shapes measured slower than the
+        library (_s3_grad_slower: the one threshold of the routing that looks at B, as B H W).  Pure, like _route."""
+        c = self.conv
+        if c.in_channels > 224 or c.out_channels > 224:
+            return None
+        route = {"conv_s3": "s3", "mfma_s3": "s3", "deconv": "deconv", "mfma_deconv": "deconv"}.get(
+            self._route(B, H, W, None, switches=(True, True)))
+        if route is None or _s3_grad_slower(route, c.in_channels, c.out_channels, B * H * W):
+            return None
+        return route
+
     def _forward_grad(self, x):
         """The forward under ``hip_grad()`` with autograd on: the same kernels, the backward recorded on ours.  None
         where the unit, the input or the shape is not covered (the caller then goes on as it always did)."""
@@ -230,6 +268,8 @@ class Unit(CachesWeights, nn.Module):
         route = self._grad_route(x0.shape[0], x0.shape[-2], x0.shape[-1], parts)
         if route is None:
             route = self._grad_route_mfma(x0.shape[0], x0.shape[-2], x0.shape[-1], parts)
+        if route is None and parts is None:
+            route = self._grad_route_s3(x0.shape[0], x0.shape[-2], x0.shape[-1])
         if route is None:
             return None
         if self.bn is not None:                                         # differentiable (fold_bn's arithmetic)
@@ -238,8 +278,13 @@ class Unit(CachesWeights, nn.Module):
             scale, shift = fold_none(c)
         n_tally = None if TALLY is None else len(TALLY)
         if TALLY is not None:
-            _tally(self, "conv_grad" if route == "conv" else "mfma_grad", x)
+            _tally(self, {"conv": "conv_grad", "mfma": "mfma_grad", "s3": "s3_grad", "deconv": "deconv_grad"}[route], x)
         try:
+            if route in ("s3", "deconv"):
+                fwd = self._route(x0.shape[0], x0.shape[-2], x0.shape[-1], None, switches=(True, True))
+                packed = self._folded_mfma() if fwd.startswith("mfma") else self._folded()
+                fn = Conv2dS3Function if route == "s3" else Deconv2dS3Function
+                return fn.apply(fwd, packed, bool(self.relu), c.weight, scale, shift, x0)
             if route == "mfma":
                 return Conv2dMfmaFunction.apply(self._folded_mfma(), c.kernel_size[0], c.dilation[0], bool(self.relu),
                                                 c.weight, scale, shift, *xs)

@@ -157,6 +157,40 @@ def conv2d_mfma_wgrad(xs, gy, y, k, dil):
     return _wgrad("conv2d_mfma_wgrad", xs, gy, y, k, dil)
 
 
+def _wgrad_s3(name, tr, x, gy, y):
+    """One stride-3 weight-gradient entry (csrc/conv2d_mfma_grad.hip): x [B,Cin,H,W], gy (and y or None) the layer's output
+    side -> (G in the layer's weight layout, gsum [Cout], gm)."""
+    B, Ci, H, W = _chk("x", x).shape
+    Co = _chk("gy", gy).shape[1]
+    _chk("gy", gy, (B, Co, 3 * H, 3 * W) if tr else (B, Co, (H - 1) // 3 + 1, (W - 1) // 3 + 1))
+    if y is not None:
+        _chk("y", y, gy.shape)
+    key = (name, B, Ci, Co, H, W)
+    nws = _WGRAD_FLOATS.get(key)
+    if nws is None:
+        nws = _WGRAD_FLOATS[key] = int(size(name + "_workspace_floats", *key[1:]))
+    if nws == 0:
+        raise _lib.DecnetHipError("decnet_%s does not cover B %d, Cin %d, Cout %d, %d x %d" % key)
+    dev = gy.device
+    G = torch.empty((Ci, Co, 3, 3) if tr else (Co, Ci, 3, 3), dtype=_F32, device=dev)
+    gsum = torch.empty((Co,), dtype=_F32, device=dev)
+    gm = gy if y is None else torch.empty_like(gy)
+    ws = torch.empty(nws, dtype=_F32, device=dev)                      # torch allocations are 16-byte aligned
+    _call("decnet_" + name, gy, x.data_ptr(), gy.data_ptr(), None if y is None else y.data_ptr(),
+          None if y is None else gm.data_ptr(), G.data_ptr(), gsum.data_ptr(), ws.data_ptr(), nws, B, Ci, Co, H, W)
+    return G, gsum, gm
+
+
+def conv2d_k3s3_wgrad(x, gy, y):
+    """Conv2d k 3, stride 3, padding 1: gy [B,Cout,ceil(H/3),ceil(W/3)] -> (G [Cout,Cin,3,3], gsum, gm)."""
+    return _wgrad_s3("conv2d_k3s3_wgrad", False, x, gy, y)
+
+
+def deconv2d_k3s3_wgrad(x, gy, y):
+    """ConvTranspose2d k 3, stride 3: gy [B,Cout,3H,3W] -> (G [Cin,Cout,3,3], gsum, gm)."""
+    return _wgrad_s3("deconv2d_k3s3_wgrad", True, x, gy, y)
+
+
 def bias_act_inplace(x, b, relu):
     B, Co, H, W = _chk("x", x).shape
     _call("decnet_bias_act_inplace", x, x.data_ptr(), _chk("bias", b, (Co,)).data_ptr(), B, Co, H, W, relu)
@@ -167,6 +201,22 @@ def s2d3_pad1(x, out=None):
     """Space to depth of a k 3, stride 3, padding 1 convolution: [B,C,H,W] -> [B,9C,ceil(H/3),ceil(W/3)]."""
     B, C, H, W = _chk("x", x).shape
     return _run("decnet_s2d3_pad1", (x,), out, (B, 9 * C, (H - 1) // 3 + 1, (W - 1) // 3 + 1), B, C, H, W)
+
+
+def d2s3_pad1(t, H, W, out=None):
+    """The adjoint of s2d3_pad1: t [B,9C,ceil(H/3),ceil(W/3)] -> [B,C,H,W], written in full."""
+    B, K, Ho, Wo = _chk("t", t).shape
+    if K % 9 or (Ho, Wo) != ((H - 1) // 3 + 1, (W - 1) // 3 + 1):
+        raise ValueError("t %s is not the space-to-depth of a %d x %d image" % (tuple(t.shape), H, W))
+    return _run("decnet_d2s3_pad1", (t,), out, (B, K // 9, H, W), B, K // 9, H, W)
+
+
+def s2d3_pad0(g, out=None):
+    """Space to depth of a k 3, stride 3 transposed convolution's output: [B,C,3H,3W] -> [B,9C,H,W]."""
+    B, C, H3, W3 = _chk("g", g).shape
+    if H3 % 3 or W3 % 3:
+        raise ValueError("g is %d x %d, not 3H x 3W" % (H3, W3))
+    return _run("decnet_s2d3_pad0", (g,), out, (B, 9 * C, H3 // 3, W3 // 3), B, C, H3 // 3, W3 // 3)
 
 
 # ---- the ASPP block as a per-tap GEMM (csrc/tapconv.hip) -------------------------------------------------------------

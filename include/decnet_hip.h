@@ -421,6 +421,34 @@ size_t decnet_conv2d_mfma_wgrad_workspace_floats(int B, int Cin, int Cout, int H
 int decnet_conv2d_mfma_wgrad(const float *const *xs, const int *cins, int nseg, const float *gy, const float *y,
                              float *gm, float *G, float *gsum, float *workspace, size_t workspace_floats, int B, int Cout,
                              int H, int W, int k, int dilation, void *stream);
+/* Weight gradients of the stride-3 layers with frozen BatchNorm (csrc/conv2d_mfma_grad.hip), with the meaning of
+ * decnet_conv2d_mfma_wgrad: gm = gy * [y > 0] (written in full; y NULL: no ReLU, gm may be NULL and is gy), G and gsum[co] =
+ * sum gm written in full, so that dW = scale * G, dscale = <w, G>, dshift = gsum.
+ * decnet_conv2d_k3s3_wgrad: Conv2d k 3, stride 3, padding 1 (the layers of decnet_conv2d_k3s3_bn_act and decnet_s2d3_pad1 +
+ * decnet_conv2d_mfma_cat_bn_act).  x [B,Cin,H,W]; gy, y, gm [B,Cout,Ho,Wo], Ho = (H-1)/3+1, Wo = (W-1)/3+1;
+ *   G[co][ci][ky][kx] = sum_{b,yo,xo} gm[b][co][yo][xo] * x[b][ci][3yo-1+ky][3xo-1+kx]   (zeros outside), G [Cout,Cin,3,3]
+ * decnet_deconv2d_k3s3_wgrad: ConvTranspose2d k 3, stride 3, padding 0 (decnet_deconv2d_k3s3_bn_act,
+ * decnet_deconv2d_mfma_k3s3_bn_act).  x [B,Cin,H,W]; gy, y, gm [B,Cout,3H,3W];
+ *   G[ci][co][a][c] = sum_{b,i,j} x[b][ci][i][j] * gm[b][co][3i+a][3j+c], G [Cin,Cout,3,3]
+ * Both are one GEMM [Cp x coarse pixels] . [coarse pixels x (9 Cq + 1)] on v_mfma_f32_16x16x4_f32 (an fp32 fma chain) of the
+ * coarse tensor (gm / x) with the 3 x 3 stride-3 windows of the fine one (x / gm), read in place.  Cin, Cout <= 224; B and
+ * the coarse H <= 65535; a fine plane < 2^29 floats.
+ *   workspace   decnet_..._k3s3_wgrad_workspace_floats(B, Cin, Cout, H, W) floats (0: shape not covered), 16-byte aligned
+ *               (else DECNET_ERR_MISALIGNED); fewer floats than the query: DECNET_ERR_BAD_SHAPE
+ * Every other buffer is accepted at any float alignment.  Deterministic: partition and order are functions of the shape
+ * alone; workgroups write partial sums (fp32 chains of at most 4096 terms: 64 coarse pixels x at most 64 chunks) into the
+ * workspace, a second launch adds them in a fixed order in float64 and rounds once; the transposed layer's gsum is a
+ * fixed-order float64 sum of gm (two more launches).  No atomics, no allocation, no synchronisation (capturable).
+ * NULL (also y without gm): DECNET_ERR_NULL_POINTER; a dimension < 1: DECNET_ERR_BAD_SHAPE (the planes of gy, y and gm
+ * follow from H and W); Cin or Cout > 224 or a size limit: DECNET_ERR_UNSUPPORTED.  Nothing is launched on any refusal. */
+size_t decnet_conv2d_k3s3_wgrad_workspace_floats(int B, int Cin, int Cout, int H, int W);
+int decnet_conv2d_k3s3_wgrad(const float *x, const float *gy, const float *y, float *gm, float *G, float *gsum,
+                             float *workspace, size_t workspace_floats, int B, int Cin, int Cout, int H, int W,
+                             void *stream);
+size_t decnet_deconv2d_k3s3_wgrad_workspace_floats(int B, int Cin, int Cout, int H, int W);
+int decnet_deconv2d_k3s3_wgrad(const float *x, const float *gy, const float *y, float *gm, float *G, float *gsum,
+                               float *workspace, size_t workspace_floats, int B, int Cin, int Cout, int H, int W,
+                               void *stream);
 /* Refinement.get_warped_feats_by_homgrp (submodule.py:719-745): out[b,c,y,x] = bilinear(right[b,c];
  * (x - disp[b,y,x]) * W/(W-1) - 0.5, y * H/(H-1) - 0.5), zero padding.  right,out [B,C,H,W], disp [B,H,W]. */
 int decnet_warp_disparity(const float *right, const float *disp, float *out, int B, int C, int H, int W,
@@ -490,6 +518,14 @@ int decnet_sigmoid_blend_backward(const float *o, const float *a, const float *b
  * out[b,c*9+ky*3+kx,yo,xo] = x[b,c,3yo-1+ky,3xo-1+kx] (0 outside); the convolution is then the 1 x 1 convolution with the
  * weight [Cout,Cin,3,3] read as [Cout,9 Cin] (decnet_conv2d_mfma_cat_bn_act, k = 1). */
 int decnet_s2d3_pad1(const float *x, float *out, int B, int C, int H, int W, void *stream);
+/* The adjoint of decnet_s2d3_pad1 (the input gradient of the stride-3 convolutions): t [B,9C,Ho,Wo] -> dx [B,C,H,W],
+ * dx[b,c,r,s] = t[b,c*9+((r+1)%3)*3+(s+1)%3,(r+1)/3,(s+1)/3], and 0 where (r+1)/3 = Ho or (s+1)/3 = Wo (the last row /
+ * column when H / W is a multiple of 3): dx is written in full.  H, B*C <= 65535 (else DECNET_ERR_UNSUPPORTED). */
+int decnet_d2s3_pad1(const float *t, float *dx, int B, int C, int H, int W, void *stream);
+/* Space-to-depth of a ConvTranspose2d k 3, stride 3, padding 0 (its input gradient is the 1 x 1 convolution 9 C -> Cin of
+ * this): g [B,C,3H,3W] -> out [B,9C,H,W], out[b,c*9+3a+j,i,x] = g[b,c,3i+a,3x+j].  H <= 21845, B*C <= 65535 (else
+ * DECNET_ERR_UNSUPPORTED). */
+int decnet_s2d3_pad0(const float *g, float *out, int B, int C, int H, int W, void *stream);
 /* y[b,c,:,:] = act(y[b,c,:,:] + shift[c]) in place, y [B,C,H,W]: the folded-BatchNorm bias and the ReLU
  * behind a library convolution, one pass.  B*C <= 65535. */
 int decnet_bias_act_inplace(float *y, const float *shift, int B, int C, int H, int W, int relu,
