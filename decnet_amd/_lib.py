@@ -14,6 +14,7 @@ _P = ctypes.c_void_p
 _I = ctypes.c_int
 _F = ctypes.c_float
 _Z = ctypes.c_size_t
+_D = ctypes.c_double
 
 # name -> argtypes  (kept in the order of include/decnet_hip.h; tests check every symbol)
 SIGNATURES = {
@@ -102,6 +103,9 @@ SIGNATURES = {
     "decnet_disparity_metrics": [_P, _P, _F, _P] + [_I] * 5 + [_P],
     "decnet_stage_loss_forward": [_P] * 7 + [_F, _F, _I] + [_P] * 3 + [_I] * 3 + [_P],
     "decnet_stage_loss_backward": [_P] * 7 + [_F, _F, _I] + [_P] * 7 + [_I] * 3 + [_P],
+    "decnet_bn_train_workspace_floats": [_I] * 4,
+    "decnet_bn_train_forward": [_P] * 3 + [_D, _D] + [_P] * 4 + [_I, _P, _Z] + [_I] * 4 + [_P],
+    "decnet_bn_train_backward": [_P] * 8 + [_I, _P, _Z] + [_I] * 4 + [_P],
 }
 
 
@@ -114,7 +118,7 @@ class Stage0Params(ctypes.Structure):
 
 ERRORS = {-1: "null pointer", -2: "bad shape", -3: "shape not supported by the gfx950 kernels",
           -4: "non-finite (NaN / Inf) element in a feature map (DECNET_CHECK_FINITE=1)",
-          -5: "library-format buffer not 16-byte aligned"}
+          -5: "library-format buffer or workspace not aligned as the entry requires"}
 
 _lib = None
 

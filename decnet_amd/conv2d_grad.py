@@ -25,7 +25,12 @@ The layers between the pyramid levels -- Conv2d k 3, stride 3, padding 1 and Con
                 dx = conv1x1(s2d3_pad0(gm), (w * scale[co]) read as [Cin, 9 Cout])           (w [Cin,Cout,3,3], no flip)
 
 with the 1 x 1 convolutions on decnet_conv2d_mfma_cat_bn_act.
-Out of scope: training-mode BatchNorm, stage 0, the ASPP tap-conv block, the 20 x 36 stride-1 layers, double backward.
+
+A unit in ``.train()`` mode (``Unit._forward_grad_train``) runs the same conv Function with scale 1, shift 0 and no ReLU,
+then ``BatchNormActFunction``: BatchNorm2d on the statistics of the batch (+ ReLU), forward and backward on
+csrc/batchnorm.hip, the running statistics updated in place by the forward kernel.
+Out of scope: BatchNorm3d (stage 0), statistics synchronised across GPUs, ``momentum=None``, the ASPP tap-conv block, the
+20 x 36 stride-1 layers, double backward.
 """
 import contextlib
 import threading
@@ -47,7 +52,9 @@ def hip_grad_enabled():
 @contextlib.contextmanager
 def hip_grad(enabled=True):
     """While active (in this thread), an eval-mode ``Unit`` that ``Unit._grad_route`` covers records its backward on the
-    HIP kernels instead of going to the library.  Nests; ``hip_grad(False)`` switches it off inside an enabled region."""
+    HIP kernels instead of going to the library, and one in ``.train()`` mode that ``Unit._grad_route_train`` covers runs
+    its BatchNorm on the statistics of the batch as ``BatchNormActFunction``.  Nests; ``hip_grad(False)`` switches it off
+    inside an enabled region."""
     old = hip_grad_enabled()
     _STATE.on = bool(enabled)
     try:
@@ -228,3 +235,32 @@ class Deconv2dS3Function(Function):
             wt = (w32 * s32.view(1, -1, 1, 1)).reshape(w32.shape[0], -1)
             dx = _conv1x1_mfma(ops2d.s2d3_pad0(gm), wt)
         return (None, None, None, dw, dscale, dshift, dx)
+
+
+class BatchNormActFunction(Function):
+    """apply(z, weight, bias, running_mean, running_var, eps, momentum, relu) -> y = act(batch_norm(z)) on the statistics
+    of the batch z [B,C,H,W] (decnet_bn_train_forward).  running_mean / running_var (both None, or both [C]) are written in
+    place by the kernel, which autograd does not see: their versions are bumped here, so the caches that fold the running
+    statistics (stage0.source_key) rebuild on the next eval forward.  ``num_batches_tracked`` is the caller's.  Gradients:
+    z, weight, bias, each only when wanted; the ReLU decision is recomputed from z, y is not saved."""
+
+    @staticmethod
+    def forward(ctx, z, weight, bias, running_mean, running_var, eps, momentum, relu):
+        z = z.contiguous()
+        y, stats = ops2d.bn_train_forward(z, weight, bias, eps, momentum, running_mean, running_var, relu)
+        if running_mean is not None:
+            torch.autograd.graph.increment_version(running_mean)
+            torch.autograd.graph.increment_version(running_var)
+        ctx.relu = bool(relu)
+        ctx.save_for_backward(z, weight, bias, stats)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        z, weight, bias, stats = ctx.saved_tensors
+        need_z, need_w, need_b = ctx.needs_input_grad[:3]
+        gz = dw = db = None
+        if need_z or need_w or need_b:
+            gz, dw, db = ops2d.bn_train_backward(z, gy.contiguous(), weight, bias, stats, ctx.relu, want_gz=need_z)
+        return (gz, dw if need_w else None, db if need_b else None, None, None, None, None, None)

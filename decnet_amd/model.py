@@ -21,7 +21,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops2d
-from .conv2d_grad import Conv2dMfmaFunction, Conv2dS3Function, Conv2dSmallFunction, Deconv2dS3Function, hip_grad_enabled
+from .conv2d_grad import (BatchNormActFunction, Conv2dMfmaFunction, Conv2dS3Function, Conv2dSmallFunction, Deconv2dS3Function,
+                          hip_grad_enabled)
 from .tail_grad import DynamicUpsample3Function, SigmoidBlendFunction, Unfold3CatFunction, WarpDisparityFunction
 from ._lib import DecnetHipError, UNSUPPORTED
 from .ops import spamatvar_forward, spamatvar_forward_bits
@@ -134,6 +135,33 @@ def _s3_grad_slower(route, cin, cout, n):
     if route == "s3":
         return cout > 24 and n >= 51840
     return cin >= 72 and 2880 <= n < 51840
+
+
+def _bn_train_slower(route, cin, cout, dil, n):
+    """The units (route: the eval-mode decision of Unit._grad_route_train; dil: the dilation; n = B H W, the pixels of the
+    unit's INPUT over the batch) that stay on the library in ``.train()`` mode under ``hip_grad()``: those whose forward +
+    backward was measured slower than the library's conv -> batch norm -> ReLU under autograd -- eager, one run
+    (tools/bench_bn_train.py, profiles/bn_train.json: every Unit of the model at config 5's sizes, B = 8 in the extractor,
+    B = 4 elsewhere; speed relative to the library eager, in brackets as GraphedStep replays).
+      * "conv" without dilation: all eleven units measured at the two smaller sizes were slower eager -- at n = 4 x 60 x 108
+        = 25920 (8 -> 3, 3 -> 3, 3 -> 1 of the mask generator, 8 -> 8, 8 -> 1 of the attention): 0.44 - 0.54 (0.42 - 0.71);
+        at n = 4 x 180 x 324 = 233280 (the same five and 12 -> 12 of the refinement): 0.54 - 0.88 (1.12 - 1.94): an eager
+        step of one unit is bound by the host at 0.31 - 0.43 ms whatever the size (some 14 small launches, the route's own
+        fills and repacks among them), against the library's 0.14 - 0.27 ms.  That verdict is carried up to the next
+        measured size, 4 x 540 x 972 = 2099520 pixels, where the fifteen units measured (there and at 8 x 540 x 972) are
+        2.68 - 7.22 x the library (3.13 - 7.26): a ninefold span in which nothing was measured.  The one dilated unit at
+        those sizes, 12 -> 12 with dilation 6 at 233280, was 1.06 (1.32) -- the library's dilated convolution is slower --
+        and stays.
+      * "mfma" (48 -> 24 at 8 x 180 x 324, 49 -> 24, 73 -> 81, 81 -> 81 at 4 x 180 x 324): 1.25 - 1.94 (1.25 - 1.94);
+        "s3" (8 -> 24 at 8 x 540 x 972): 2.57 (2.59); "deconv" (72 -> 24 at 8 x 60 x 108, 24 -> 8 at 8 x 180 x 324): 1.36, 6.43
+        (1.56, 6.52): none goes back.  The units the eval-mode exclusions (_mfma_grad_slower, _s3_grad_slower) keep on the
+        library were not measured in train mode and stay there.
+    Below 25920 pixels nothing is excluded (nothing was measured there): the floor is the forward route's, where the tests
+    run; a caller with one small image is bound by the host there and gains nothing."""
+    return route == "conv" and dil == 1 and 25920 <= n < 2099520
+
+
+_GRAD_FAMILY = {"conv": "conv_grad", "mfma": "mfma_grad", "s3": "s3_grad", "deconv": "deconv_grad"}
 
 
 def _same_padded(c):
@@ -255,21 +283,67 @@ class Unit(CachesWeights, nn.Module):
             return None
         return route
 
-    def _forward_grad(self, x):
-        """The forward under ``hip_grad()`` with autograd on: the same kernels, the backward recorded on ours.  None
-        where the unit, the input or the shape is not covered (the caller then goes on as it always did)."""
+    def _grad_route_train(self, B, H, W, parts=None):
+        """The route ("conv" / "mfma" / "s3" / "deconv") of a unit in ``.train()`` mode under ``hip_grad()``
+        (_forward_grad_train: the conv Function of that route with scale 1, shift 0 and no ReLU, then
+        conv2d_grad.BatchNormActFunction), else None.  Only a unit whose ``bn`` is affine, tracks its running statistics
+        and has a float momentum; the route is the eval-mode decision -- _grad_route, then _grad_route_mfma, then
+        _grad_route_s3, with their measured exclusions -- less the units measured slower than the library in train mode
+        (_bn_train_slower).  Pure, like _route."""
+        bn = self.bn
+        if bn is None or not bn.affine or not bn.track_running_stats or not isinstance(bn.momentum, float):
+            return None
+        route = self._grad_route_any(B, H, W, parts)
+        c = self.conv
+        if route is None or _bn_train_slower(route, c.in_channels, c.out_channels, c.dilation[0], B * H * W):
+            return None
+        return route
+
+    def _grad_route_any(self, B, H, W, parts=None):
+        """The eval-mode decision under ``hip_grad()``: _grad_route, then _grad_route_mfma, then (one tensor) _grad_route_s3."""
+        route = self._grad_route(B, H, W, parts)
+        if route is None:
+            route = self._grad_route_mfma(B, H, W, parts)
+        if route is None and parts is None:
+            route = self._grad_route_s3(B, H, W)
+        return route
+
+    def _grad_inputs(self, x):
+        """-> (the parts of x as a tuple, their number or None for a single tensor) when the HIP Functions take them: float32
+        tensors [B,c_i,H,W] of one batch, size and GPU, the weights float32; else None."""
         xs = tuple(x) if isinstance(x, (tuple, list)) else (x,)
-        x0, c = xs[0], self.conv
-        if not (x0.is_cuda and c.weight.dtype == torch.float32) or any(
+        x0 = xs[0]
+        if not (x0.is_cuda and self.conv.weight.dtype == torch.float32) or any(
                 t.dim() != 4 or t.dtype != torch.float32 or t.device != x0.device or t.shape[0] != x0.shape[0] or
                 t.shape[2:] != x0.shape[2:] for t in xs):
             return None
-        parts = len(xs) if isinstance(x, (tuple, list)) else None
-        route = self._grad_route(x0.shape[0], x0.shape[-2], x0.shape[-1], parts)
-        if route is None:
-            route = self._grad_route_mfma(x0.shape[0], x0.shape[-2], x0.shape[-1], parts)
-        if route is None and parts is None:
-            route = self._grad_route_s3(x0.shape[0], x0.shape[-2], x0.shape[-1])
+        return xs, (len(xs) if isinstance(x, (tuple, list)) else None)
+
+    def _apply_grad_route(self, route, xs, relu, scale, shift, unfolded=False):
+        """The conv Function of `route` on the parts xs.  scale, shift: what the Function differentiates; unfolded: they are
+        also what the forward kernel applies (constants), in place of the cache's folded BatchNorm."""
+        x0, c = xs[0], self.conv
+        fold = (lambda p: (p[0], scale, shift)) if unfolded else (lambda p: p)
+        if route in ("s3", "deconv"):
+            fwd = self._route(x0.shape[0], x0.shape[-2], x0.shape[-1], None, switches=(True, True))
+            packed = fold(self._folded_mfma() if fwd.startswith("mfma") else self._folded())
+            fn = Conv2dS3Function if route == "s3" else Deconv2dS3Function
+            return fn.apply(fwd, packed, relu, c.weight, scale, shift, x0)
+        if route == "mfma":
+            return Conv2dMfmaFunction.apply(fold(self._folded_mfma()), c.kernel_size[0], c.dilation[0], relu, c.weight,
+                                            scale, shift, *xs)
+        return Conv2dSmallFunction.apply(fold(self._folded()), c.kernel_size[0], c.dilation[0], relu, c.weight, scale,
+                                         shift, *xs)
+
+    def _forward_grad(self, x):
+        """The forward under ``hip_grad()`` with autograd on: the same kernels, the backward recorded on ours.  None
+        where the unit, the input or the shape is not covered (the caller then goes on as it always did)."""
+        ins = self._grad_inputs(x)
+        if ins is None:
+            return None
+        xs, parts = ins
+        x0, c = xs[0], self.conv
+        route = self._grad_route_any(x0.shape[0], x0.shape[-2], x0.shape[-1], parts)
         if route is None:
             return None
         if self.bn is not None:                                         # differentiable (fold_bn's arithmetic)
@@ -278,24 +352,50 @@ class Unit(CachesWeights, nn.Module):
             scale, shift = fold_none(c)
         n_tally = None if TALLY is None else len(TALLY)
         if TALLY is not None:
-            _tally(self, {"conv": "conv_grad", "mfma": "mfma_grad", "s3": "s3_grad", "deconv": "deconv_grad"}[route], x)
+            _tally(self, _GRAD_FAMILY[route], x)
         try:
-            if route in ("s3", "deconv"):
-                fwd = self._route(x0.shape[0], x0.shape[-2], x0.shape[-1], None, switches=(True, True))
-                packed = self._folded_mfma() if fwd.startswith("mfma") else self._folded()
-                fn = Conv2dS3Function if route == "s3" else Deconv2dS3Function
-                return fn.apply(fwd, packed, bool(self.relu), c.weight, scale, shift, x0)
-            if route == "mfma":
-                return Conv2dMfmaFunction.apply(self._folded_mfma(), c.kernel_size[0], c.dilation[0], bool(self.relu),
-                                                c.weight, scale, shift, *xs)
-            return Conv2dSmallFunction.apply(self._folded(), c.kernel_size[0], c.dilation[0], bool(self.relu), c.weight,
-                                             scale, shift, *xs)
+            return self._apply_grad_route(route, xs, bool(self.relu), scale, shift)
         except DecnetHipError as e:                     # the grid limits of the forward kernel: the library takes it
             if e.code != UNSUPPORTED:
                 raise
             if n_tally is not None:
                 del TALLY[n_tally:]
             return None
+
+    def _forward_grad_train(self, x):
+        """The forward of a unit in ``.train()`` mode under ``hip_grad()`` with autograd on: the convolution as the conv
+        Function of _grad_route_train (scale 1, shift 0 as constants, no ReLU: its backward launches the weight gradient
+        for dW alone), then BatchNormActFunction on the statistics of the batch, which also updates the running statistics;
+        ``num_batches_tracked`` is counted here.  None where the unit, the input or the shape is not covered, or ``bn``
+        itself is in eval mode (the caller then goes on as it always did; nothing has been updated)."""
+        ins = self._grad_inputs(x)
+        if ins is None or self.bn is None or not self.bn.training or self.bn.weight.dtype != torch.float32:
+            return None
+        xs, parts = ins
+        x0, c, bn = xs[0], self.conv, self.bn
+        route = self._grad_route_train(x0.shape[0], x0.shape[-2], x0.shape[-1], parts)
+        if route is None:
+            return None
+        ones = torch.ones(c.out_channels, device=x0.device)
+        zeros = torch.zeros(c.out_channels, device=x0.device)
+        n_tally = None if TALLY is None else len(TALLY)
+        if TALLY is not None:
+            _tally(self, _GRAD_FAMILY[route], x)
+        try:
+            z = self._apply_grad_route(route, xs, False, ones, zeros, unfolded=True)
+        except DecnetHipError as e:                     # the grid limits of the forward kernel: the library takes it
+            if e.code != UNSUPPORTED:
+                raise
+            if n_tally is not None:
+                del TALLY[n_tally:]
+            return None
+        if TALLY is not None:                           # z read twice and y written once; two sums and one fma per element
+            TALLY.append({"family": "bn_train", "flops": 8.0 * z.numel(), "bytes": 12.0 * z.numel()})
+        y = BatchNormActFunction.apply(z, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum,
+                                       bool(self.relu))
+        with torch.no_grad():
+            bn.num_batches_tracked.add_(1)
+        return y
 
     def _sources(self):
         c, bn = self.conv, self.bn
@@ -381,8 +481,14 @@ class Unit(CachesWeights, nn.Module):
         return ops2d.conv2d_bn_act(x.contiguous(), *wss, ci, k, dil, relu, out=out)
 
     def forward(self, x):
-        if hip_grad_enabled() and not self.training and torch.is_grad_enabled():
-            y = self._forward_grad(x)
+        if hip_grad_enabled() and torch.is_grad_enabled():
+            # (without bn the training flag changes nothing: the eval route, and its bits.  A training unit whose bn was put
+            # into eval mode -- frozen statistics inside model.train() -- goes on as it always did: the library's
+            # convolution and bn(x) on the running statistics, nothing written)
+            if not self.training or self.bn is None:
+                y = self._forward_grad(x)
+            else:
+                y = self._forward_grad_train(x) if self.bn.training else None
             if y is not None:
                 return y
         kind = self._hip_kind(x)
@@ -670,7 +776,7 @@ class SoftAttention(nn.Module):
         of the three convolution launches."""
         parts = (fea, dense.unsqueeze(1), sparse.unsqueeze(1), mask.unsqueeze(1), var.unsqueeze(1))
         u0, u1, u2 = self.conv[0], self.conv[1], self.conv[2]
-        if not self.training and u2.conv.out_channels == 1 and not u2.relu and tail_grad_gate(*parts):
+        if u2.conv.out_channels == 1 and not u2.relu and tail_grad_gate(*parts):
             y = self._fuse_grad(parts, dense, sparse)
             if y is not None:
                 return y
@@ -695,19 +801,34 @@ class SoftAttention(nn.Module):
         return (u2.conv.out_channels == 1 and not u2.relu and u0._grad_route(B, H, W, 5) == "conv" and
                 u1._grad_route(B, H, W) == "conv" and u2._grad_route(B, H, W) == "conv")
 
+    def _fuse_grad_route_train(self, B, H, W):
+        """The same in ``.train()`` mode: every unit with BatchNorm on Unit._grad_route_train's "conv" (batch statistics), one
+        without as in eval mode.  Pure."""
+        u0, u1, u2 = self.conv[0], self.conv[1], self.conv[2]
+        route = lambda u, parts=None: (u._grad_route_train if u.bn is not None else u._grad_route)(B, H, W, parts)  # noqa: E731
+        return (u2.conv.out_channels == 1 and not u2.relu and route(u0, 5) == "conv" and route(u1) == "conv" and
+                route(u2) == "conv")
+
     def _fuse_grad(self, parts, dense, sparse):
-        """fuse() on the route of _fuse_grad_route; None where it does not hold (the caller goes on as it always did)."""
+        """fuse() on the route of _fuse_grad_route (_fuse_grad_route_train in ``.train()`` mode); None where it does not
+        hold (the caller goes on as it always did)."""
         B, _, H, W = parts[0].shape
-        if any(u.training for u in self.conv) or not self._fuse_grad_route(B, H, W):
+        train = self.training
+        if any(u.training != train or (train and u.bn is not None and not u.bn.training) for u in self.conv):
+            return None                                 # (e.g. frozen BatchNorms inside a training module: the usual route)
+        if not (self._fuse_grad_route_train(B, H, W) if train else self._fuse_grad_route(B, H, W)):
             return None
         n_tally = None if TALLY is None else len(TALLY)
         t = parts[:4] + (-parts[4],)
         for u in self.conv:
-            t = u._forward_grad(t)
-            if t is None:                               # a grid limit of the forward kernel: the usual route, from the start
+            y = u._forward_grad_train(t) if train and u.bn is not None else u._forward_grad(t)
+            if y is None and train:                     # a grid limit of the forward kernel: this unit alone goes the usual
+                y = u(t)                                # way -- the units before it have updated their running statistics
+            elif y is None:                             # ... in eval mode: the usual route, from the start
                 if n_tally is not None:
                     del TALLY[n_tally:]
                 return None
+            t = y
         return SigmoidBlendFunction.apply(t.squeeze(1), dense, sparse)
 
 

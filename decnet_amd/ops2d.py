@@ -191,6 +191,48 @@ def deconv2d_k3s3_wgrad(x, gy, y):
     return _wgrad_s3("deconv2d_k3s3_wgrad", True, x, gy, y)
 
 
+# ---- training-mode BatchNorm + ReLU under hip_grad() (csrc/batchnorm.hip; the Function is in conv2d_grad.py) -------------
+BN_SEGMENT = 4096                  # DECNET_BN_SEGMENT of include/decnet_hip.h: floats of a plane one wave sums
+
+
+def _bn_train_args(z, weight, bias):
+    B, C, H, W = _chk("z", z).shape
+    _chk("weight", weight, (C,))
+    _chk("bias", bias, (C,))
+    nws = int(size("bn_train_workspace_floats", B, C, H, W))             # 0: a shape the entry refuses (it says which)
+    ws = torch.empty(max(nws, 2), dtype=_F32, device=z.device)           # torch allocations are 16-byte aligned
+    return (B, C, H, W), ws, nws
+
+
+def bn_train_forward(z, weight, bias, eps, momentum, running_mean, running_var, relu):
+    """Batch-statistics BatchNorm2d (+ ReLU) of z [B,C,H,W] -> (y, stats [2C] float64: {mean, invstd} per channel, what
+    bn_train_backward reads).  running_mean / running_var: both None, or both [C], updated in place.  The workspace comes
+    from torch.empty per call, its size from the library's query."""
+    dims, ws, nws = _bn_train_args(z, weight, bias)
+    if (running_mean is None) != (running_var is None):
+        raise ValueError("running_mean and running_var go together")
+    stats = torch.empty(2 * dims[1], dtype=torch.float64, device=z.device)
+    y = torch.empty_like(z)
+    _call("decnet_bn_train_forward", z, z.data_ptr(), weight.data_ptr(), bias.data_ptr(), float(eps), float(momentum),
+          _opt("running_mean", running_mean, (dims[1],)), _opt("running_var", running_var, (dims[1],)), stats.data_ptr(),
+          y.data_ptr(), 1 if relu else 0, ws.data_ptr(), nws, *dims)
+    return y, stats
+
+
+def bn_train_backward(z, gy, weight, bias, stats, relu, want_gz=True):
+    """-> (gz [B,C,H,W] or None, dweight [C], dbias [C]); the ReLU decision is recomputed from z, as the forward made it."""
+    dims, ws, nws = _bn_train_args(z, weight, bias)
+    _chk("gy", gy, z.shape)
+    if not (isinstance(stats, torch.Tensor) and stats.is_cuda and stats.dtype is torch.float64 and stats.is_contiguous() and
+            stats.shape == (2 * dims[1],)):
+        raise TypeError("stats must be the contiguous float64 [2 C] tensor of bn_train_forward, on the GPU")
+    gz = torch.empty_like(z) if want_gz else None
+    dw, db = torch.empty_like(weight), torch.empty_like(bias)
+    _call("decnet_bn_train_backward", z, z.data_ptr(), gy.data_ptr(), weight.data_ptr(), bias.data_ptr(), stats.data_ptr(),
+          gz.data_ptr() if want_gz else None, dw.data_ptr(), db.data_ptr(), 1 if relu else 0, ws.data_ptr(), nws, *dims)
+    return gz, dw, db
+
+
 def bias_act_inplace(x, b, relu):
     B, Co, H, W = _chk("x", x).shape
     _call("decnet_bias_act_inplace", x, x.data_ptr(), _chk("bias", b, (Co,)).data_ptr(), B, Co, H, W, relu)

@@ -640,6 +640,40 @@ int decnet_stage_loss_backward(const float *pred, const float *dense, const floa
                                float *g_dense, float *g_sparse, float *g_fusion, float *g_soft, int B, int H, int W,
                                void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Training-mode BatchNorm2d (batch statistics) with an optional ReLU, forward and backward (csrc/batchnorm.hip).
+ * z [B,C,H,W] fp32 at any float alignment: the convolution's output; N = B H W values per channel.  Neither entry
+ * allocates, synchronises or asks about the stream (both run under stream capture); sums are float64 in a fixed order
+ * without atomics, so the results depend neither on the launch shape nor on the alignment of a plane.  A NaN in a channel
+ * reaches that channel's statistics and no other's.
+ *   workspace  decnet_bn_train_workspace_floats(B,C,H,W) floats (doubles count as two), 8-byte aligned (else
+ *              DECNET_ERR_MISALIGNED); fewer floats than the query: DECNET_ERR_BAD_SHAPE.  It holds the partial sums
+ *              [C][B nseg][2] of the segments of DECNET_BN_SEGMENT floats a plane is cut into (nseg per plane), then [C][2]
+ *              totals.  The query returns 0 for a shape the entries refuse.
+ *   stats      [2 C] float64, 8-byte aligned: per channel {mean, invstd = 1 / sqrt(var + eps)}, var the biased variance
+ *              S2 / N - (S1 / N)^2 clamped at 0, S1 = sum (z - p), S2 = sum (z - p)^2 about the pivot p = z[0,c,0,0].
+ * DECNET_ERR_BAD_SHAPE: a dimension < 1, N < 2 (one value per channel has no variance), B C H W >= 2^31.  A NULL
+ * argument (other than those stated): DECNET_ERR_NULL_POINTER.  Nothing is launched on any refusal.
+ *
+ * decnet_bn_train_forward: three launches.
+ *   y = act(fma(d, a, beta)), d = (float)(z - mean) with the difference in float64, a = (float)(gamma invstd),
+ *   act = ReLU (relu != 0) or the identity.
+ *   running_mean, running_var   both NULL, or both [C] fp32, updated in place (float64, rounded once):
+ *              rm <- (1 - momentum) rm + momentum mean,  rv <- (1 - momentum) rv + momentum var N / (N - 1).
+ * decnet_bn_train_backward: three launches (two when gz is NULL).  With pre recomputed from z exactly as the forward formed
+ * it, gm = gy [pre > 0] (gm = gy without ReLU) and xhat = (z - mean) invstd:
+ *   dbeta = sum gm, dgamma = sum gm xhat    [C] fp32, each the fp32 of a float64 sum
+ *   gz    NULL (skipped) or [B,C,H,W], written in full: a (gm - dbeta / N - xhat dgamma / N), formed in float64.
+ * ------------------------------------------------------------------------------------- */
+#define DECNET_BN_SEGMENT 4096
+size_t decnet_bn_train_workspace_floats(int B, int C, int H, int W);
+int decnet_bn_train_forward(const float *z, const float *gamma, const float *beta, double eps, double momentum,
+                            float *running_mean, float *running_var, double *stats, float *y, int relu, void *workspace,
+                            size_t workspace_floats, int B, int C, int H, int W, void *stream);
+int decnet_bn_train_backward(const float *z, const float *gy, const float *gamma, const float *beta, const double *stats,
+                             float *gz, float *dgamma, float *dbeta, int relu, void *workspace, size_t workspace_floats,
+                             int B, int C, int H, int W, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
