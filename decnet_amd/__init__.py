@@ -8,7 +8,8 @@
 * hip_grad(): opt-in backward of the few-channel stride-1 conv units with frozen BatchNorm (Conv2dSmallFunction): the
   weight gradient as a deterministic fp32 matrix-core reduction, dx on the forward kernel with flipped weights; and of
   the full-resolution tail (WarpDisparityFunction, Unfold3CatFunction, DynamicUpsample3Function, SigmoidBlendFunction):
-  the inference entries forward, fixed-order gathers backward
+  the inference entries forward, fixed-order gathers backward; and of stage 0 (Conv3dFunction, CostVolumeFunction: the
+  eight Conv3d units of CostRegNetNoDown with frozen BatchNorm3d, the per-layer inference entries forward)
 
 Host side is Python on PyTorch-ROCm (device memory + streams only); all arithmetic runs in
 hand-written HIP kernels behind the C ABI of include/decnet_hip.h.  No CPU fallback.
@@ -24,6 +25,7 @@ from .loss import Loss, StageLossFunction  # noqa: F401
 from .conv2d_grad import Conv2dSmallFunction, hip_grad, hip_grad_enabled  # noqa: F401
 from .tail_grad import (DynamicUpsample3Function, SigmoidBlendFunction, Unfold3CatFunction,  # noqa: F401
                         WarpDisparityFunction)
+from .stage0_grad import Conv3dFunction, CostVolumeFunction  # noqa: F401
 from .stage0 import (CostRegNetNoDown, GetCostVolume, Stage0, disparity_regression,  # noqa: F401
                      drop_weight_caches, get_disp_samples)
 
@@ -31,4 +33,4 @@ __all__ = ["SpaMat", "SpaVar", "SpaMatFunction", "SpaVarFunction", "spamatvar_fo
            "GetCostVolume", "CostRegNetNoDown", "disparity_regression", "get_disp_samples",
            "Stage0", "DecnetHipError", "version", "drop_weight_caches", "StereoEngine", "Loss",
            "StageLossFunction", "Conv2dSmallFunction", "hip_grad", "hip_grad_enabled", "WarpDisparityFunction",
-           "Unfold3CatFunction", "DynamicUpsample3Function", "SigmoidBlendFunction"]
+           "Unfold3CatFunction", "DynamicUpsample3Function", "SigmoidBlendFunction", "Conv3dFunction", "CostVolumeFunction"]

@@ -74,6 +74,8 @@ SIGNATURES = {
     "decnet_conv2d_k3s3_wgrad": [_P] * 7 + [_Z] + [_I] * 5 + [_P],
     "decnet_deconv2d_k3s3_wgrad_workspace_floats": [_I] * 5,
     "decnet_deconv2d_k3s3_wgrad": [_P] * 7 + [_Z] + [_I] * 5 + [_P],
+    "decnet_conv3d_wgrad_workspace_floats": [_I] * 6,
+    "decnet_conv3d_wgrad": [_P] * 7 + [_Z] + [_I] * 6 + [_P],
     "decnet_conv2d_mfma_packed_bytes": [_I] * 3,
     "decnet_conv2d_mfma_pack_weight": [_P, _P] + [_I] * 3 + [_P],
     "decnet_conv2d_mfma_cat_bn_act": [_P, _P, _I, _P, _P, _P, _P] + [_I] * 7 + [_P],

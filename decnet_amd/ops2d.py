@@ -448,6 +448,32 @@ def conv3d_bn_act(src, w, scale, shift, res, dst, dims, Ci, Co, relu, ws=None, v
         _call("decnet_conv3d_wino_bn_act", src, *p, _chk("ws", ws).data_ptr(), *dims, Ci, Co, relu, variant)
 
 
+def conv3d_wgrad(x, gy, y, dims, Ci, Co):
+    """Weight-gradient reduction of one Conv3dUnit (decnet_conv3d_wgrad, csrc/conv3d_grad.hip) on channels-last volumes,
+    dims = (B, D, H, W): x [B,D,H,W,Ci], gy [B,D,H,W,Co], y the unit's output (the ReLU mask y > 0) or None -> (G
+    [Co,Ci,3,3,3], gsum [Co], gm = gy * [y > 0]; gy itself without y).  The workspace comes from torch.empty, its size from
+    the library's query, cached per shape."""
+    dims = tuple(int(d) for d in dims)
+    _chk("x", x, dims + (Ci,))
+    _chk("gy", gy, dims + (Co,))
+    if y is not None:
+        _chk("y", y, dims + (Co,))
+    key = ("conv3d_wgrad",) + dims + (int(Ci), int(Co))
+    nws = _WGRAD_FLOATS.get(key)
+    if nws is None:
+        nws = _WGRAD_FLOATS[key] = int(size("conv3d_wgrad_workspace_floats", *key[1:]))
+    if nws == 0:
+        raise _lib.DecnetHipError("decnet_%s does not cover B %d, D %d, %d x %d, Ci %d, Co %d" % key)
+    dev = gy.device
+    G = torch.empty((Co, Ci, 3, 3, 3), dtype=_F32, device=dev)
+    gsum = torch.empty((Co,), dtype=_F32, device=dev)
+    gm = gy if y is None else torch.empty_like(gy)
+    ws = torch.empty(nws, dtype=_F32, device=dev)                      # torch allocations are 16-byte aligned
+    _call("decnet_conv3d_wgrad", gy, x.data_ptr(), gy.data_ptr(), None if y is None else y.data_ptr(),
+          None if y is None else gm.data_ptr(), G.data_ptr(), gsum.data_ptr(), ws.data_ptr(), nws, *dims, Ci, Co)
+    return G, gsum, gm
+
+
 def conv3d_wino_stack_bn_act(x, layers, res_src, res_dst, out, ws, dims, C, variant):
     """The C -> C units `layers` (dicts of u, scale, shift) as ONE fused stack; False: "unsupported", nothing launched."""
     n = dims[0] * dims[1] * dims[2] * dims[3] * C

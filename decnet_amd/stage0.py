@@ -10,8 +10,11 @@ reference loads unchanged.  Activations between the HIP kernels are channels-las
 [B,D,H,W,C]; tensors handed back to callers have the reference's logical shapes
 ([B,C,D,H,W] cost volume is returned as a permuted view of the channels-last buffer).
 
-Inference (eval mode, no autograd) only: the reference's training path through these
-modules is not runnable as shipped and is outside the hot-path scope.
+Eval mode only (the reference's training path through these modules is not runnable as shipped).
+Under ``torch.no_grad()`` this is the inference hot path.  Inside ``decnet_amd.hip_grad()``, with autograd on and an input
+or a parameter that requires grad, ``CostRegNetNoDown`` records its backward unit by unit (``_units_grad``,
+stage0_grad.py): gradients of the feature maps, the eight ``conv.weight`` and the BatchNorm weights and biases, with the
+running statistics frozen.  Training-mode BatchNorm3d and cost_func "cat" stay refused under grad.
 """
 import os
 
@@ -19,7 +22,8 @@ import torch
 import torch.nn as nn
 from torch.optim.optimizer import register_optimizer_step_post_hook
 
-from . import _lib, ops2d
+from . import _lib, ops2d, stage0_grad
+from .conv2d_grad import hip_grad_enabled
 from .ops import _chk
 
 BN_EPS = 1e-5
@@ -166,6 +170,15 @@ def conv_algo(D=None):
     return a
 
 
+def _conv3d_grad_slower(C, voxels):
+    """The Conv3dUnit shapes (C channels, B D H W voxels) that go to the library arm (``stage0_grad.unit_library``) under
+    ``hip_grad()``: those whose forward + backward was measured slower on the HIP Function than under torch's autograd --
+    eager, one run (tools/bench_stage0_grad.py, profiles/stage0_grad.json).  The measured pairs, hip / library ms, C = 216 on
+    20 x 36 x 8: 216 -> 216 1.20 / 6.99 at 23 040 voxels and 2.21 / 13.07 at 46 080; 216 -> 1 0.49 / 4.41 and 0.54 / 8.25.
+    None is slower, and nothing is routed at a size nobody measured: every unit stays on the HIP Function."""
+    return False
+
+
 def get_disp_samples(max_dis, feature_map, stage_id=0, disprity_map=None, step=1, samp_num=9,
                      sample_spa_size=None):
     """submodule.py:376-424, stage-0 branch (:389-390): arange(max_dis) broadcast to
@@ -247,7 +260,7 @@ class CostRegNetNoDown(CachesWeights, nn.Module):
     """forward: regularise the cost volume  (submodule.py:608-662)
     args:    x: cost volume, N*C*S*H*W
     return:  regularised cost volume, N*S*H*W"""
-    _CACHE_ATTRS = cache_attrs("_packed") + ("_ws",)
+    _CACHE_ATTRS = cache_attrs("_packed", "_packed_grad") + ("_ws",)
 
     def __init__(self, in_channels, base_channels, cost_func, down_scale=3):
         super(CostRegNetNoDown, self).__init__()
@@ -267,6 +280,8 @@ class CostRegNetNoDown(CachesWeights, nn.Module):
         self._packed_key = None
         self._packed_src = None
         self._ws = {}
+        for a in cache_attrs("_packed_grad"):
+            self.__dict__.pop(a, None)
 
     def __getstate__(self):
         state = super().__getstate__()
@@ -355,9 +370,9 @@ class CostRegNetNoDown(CachesWeights, nn.Module):
     def run_ndhwc(self, x, want_reg=True, want_pred=True):
         """x: channels-last cost volume [B,D,H,W,C].  Returns (reg [B,D,H,W] or None,
         pred [B,H,W] or None).  The input buffer is not modified."""
-        if self.training or (torch.is_grad_enabled() and x.requires_grad):
-            raise NotImplementedError("CostRegNetNoDown on gfx950 is inference-only: call "
-                                      ".eval() and run under torch.no_grad()")
+        if self._grad_mode(x):
+            reg = self._units_grad(x)[-1][..., 0]
+            return (reg if want_reg else None), (self._softargmax(reg) if want_pred else None)
         _chk("cost volume", x)
         B, D, H, W, C = x.shape
         algo = conv_algo(D)
@@ -411,17 +426,83 @@ class CostRegNetNoDown(CachesWeights, nn.Module):
         return ops2d.conv3d_wino_stack_bn_act(x, P[:7], 1, 4, out, self._grow(("wino", x.device), n), dims, C, var)
 
     def forward(self, x):
+        if self._grad_mode(x):
+            y = _ndhwc_view(x)                               # (under grad: a differentiable permute, no copy kernel)
+            return self.run_ndhwc(y if y is not None else x.permute(0, 2, 3, 4, 1).contiguous(), True, False)[0]
         reg, _ = self.run_ndhwc(_to_ndhwc(x), want_reg=True, want_pred=False)
         return reg
+
+    # ---- the grad path (hip_grad(), eval mode): one Conv3dFunction per unit, stage0_grad.py -----------------------------
+    def _grad_mode(self, *inputs):
+        """Whether this call records a backward: eval mode, inside ``hip_grad()``, autograd on, and an input or a parameter
+        requires grad.  Raises where a gradient is asked for and cannot be had."""
+        if self.training:
+            raise NotImplementedError("CostRegNetNoDown on gfx950 runs in eval mode only (frozen BatchNorm3d; training-mode "
+                                      "BatchNorm3d is not implemented): call .eval()")
+        if not torch.is_grad_enabled():
+            return False
+        if hip_grad_enabled():
+            return any(t.requires_grad for t in inputs) or any(p.requires_grad for p in self.parameters())
+        if any(t.requires_grad for t in inputs):
+            raise NotImplementedError("CostRegNetNoDown on gfx950 is inference-only outside decnet_amd.hip_grad(): run under "
+                                      "torch.no_grad(), or inside hip_grad() for the gradients of stage 0")
+        return False
+
+    def _softargmax(self, reg):
+        """disparity_regression over arange(D) in torch ops: reg [B,D,H,W] -> pred [B,H,W]."""
+        D = reg.shape[1]
+        return (torch.softmax(reg, 1) * torch.arange(D, dtype=reg.dtype, device=reg.device).view(1, D, 1, 1)).sum(1)
+
+    def _pack_grad(self, variant):
+        return [stage0_grad.unit_operands(u.conv.weight.detach().float().contiguous(), variant, last=(i == 7))
+                for i, u in enumerate(self.units())]
+
+    def _units_grad(self, x):
+        """The eight units on a channels-last volume x [B,D,H,W,C] under autograd -> [y0 .. y6, reg]: every unit's output
+        ([B,D,H,W,C]; reg [B,D,H,W,1]), y4 before the residual is added (so that y_i > 0 is unit i's ReLU mask).  The
+        forward operands are packed from the weights alone and cached like ``prepare()``'s; scale and shift are
+        differentiable expressions of the BatchNorm parameters, formed per call."""
+        if self.cost_func == "cat":
+            raise NotImplementedError(stage0_grad._REFUSED % "cat")
+        units = self.units()
+        _chk("cost volume", x.detach())
+        B, D, H, W, C = x.shape
+        c_true = int(units[0].conv.weight.shape[1])
+        if C != c_true:
+            raise ValueError("cost volume has %d channels, module expects %d" % (C, c_true))
+        if C % 4:
+            raise NotImplementedError("the gradients of stage 0 take channel counts in fours (the kernels move channels in "
+                                      "16-byte groups); this module has %d" % C)
+        variant = WINO_VARIANT.get(conv_algo(D))
+        P = self._cached("_packed_grad", [u.conv.weight for u in units], [], lambda: self._pack_grad(variant),
+                         head=(variant,))
+        ws = None
+        if variant is not None:
+            ws = self._grow(("wino", x.device), ops2d.size("conv3d_wino_workspace_floats", B, D, H, W, C, C, variant))
+        outs, cur, keep = [], x, None
+        for i, u in enumerate(units):
+            scale, shift = fold_bn(u.bn)
+            if _conv3d_grad_slower(C, B * D * H * W):
+                y = stage0_grad.unit_library(cur, u.conv.weight, scale, shift, bool(u.relu))
+            else:
+                y = stage0_grad.Conv3dFunction.apply(dict(P[i], ws=ws), bool(u.relu), u.conv.weight, scale, shift, cur)
+            outs.append(y)
+            cur = y + keep if i == 4 else y                  # conv1(output0) + output0, after the ReLU
+            if i == 1:
+                keep = y
+        return outs
 
     def stage0(self, left_feature_map, right_feature_map, max_disp, return_reg=False):
         """SparseDenseNetRefinementMask.forward :127-137 in one call: cost volume (stage-0 ``arange``
         samples) -> this regulariser -> soft-argmax, through the single C entry ``decnet_stage0_forward_cf``
         (one workspace, one ctypes call; the module's cost_func picks the volume).  [B,C,H,W] x2 -> pred [B,H,W] (, reg [B,D,H,W])."""
-        if self.training or (torch.is_grad_enabled() and (left_feature_map.requires_grad or
-                                                          right_feature_map.requires_grad)):
-            raise NotImplementedError("CostRegNetNoDown on gfx950 is inference-only: call "
-                                      ".eval() and run under torch.no_grad()")
+        if self._grad_mode(left_feature_map, right_feature_map):
+            if self.cost_func == "cat":
+                raise NotImplementedError(stage0_grad._REFUSED % "cat")
+            cv = stage0_grad.CostVolumeFunction.apply(left_feature_map, right_feature_map, int(max_disp), self.cost_func)
+            reg = self._units_grad(cv)[-1][..., 0]
+            pred = self._softargmax(reg)
+            return (pred, reg) if return_reg else pred
         left, right = left_feature_map.contiguous(), right_feature_map.contiguous()
         _chk("left_feature_map", left)
         if left.shape[1] % 4:                           # see prepare()

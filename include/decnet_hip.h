@@ -449,6 +449,31 @@ size_t decnet_deconv2d_k3s3_wgrad_workspace_floats(int B, int Cin, int Cout, int
 int decnet_deconv2d_k3s3_wgrad(const float *x, const float *gy, const float *y, float *gm, float *G, float *gsum,
                                float *workspace, size_t workspace_floats, int B, int Cin, int Cout, int H, int W,
                                void *stream);
+/* Weight gradient of one stage-0 Conv3dUnit with frozen BatchNorm (csrc/conv3d_grad.hip): the 3-D, channels-last
+ * counterpart of decnet_conv2d_mfma_wgrad for y = act(conv(x, w) * scale + shift), Conv3d k 3, s 1, p 1.
+ *   x [B,D,H,W,Ci];  gy, y, gm [B,D,H,W,Co];  G [Co,Ci,3,3,3] (torch layout);  gsum [Co]
+ *   gm = gy * [y > 0] (written in full; y NULL: no ReLU, gm may be NULL and is gy)
+ *   G[co][ci][kd][kh][kw] = sum_{b,d,h,w} gm[b,d,h,w,co] * x[b,d+kd-1,h+kh-1,w+kw-1,ci]   (zeros outside the volume)
+ *   gsum[co] = sum gm[...,co];  G and gsum written in full, so that dW = scale * G, dscale = <w, G>, dshift = gsum.
+ * dx is the forward entry itself (decnet_conv3d_bn_act / decnet_conv3d_wino_bn_act) on gm with scale 1, shift 0, no ReLU and
+ * the weights w'[ci][co][kd][kh][kw] = w[co][ci][2-kd][2-kh][2-kw] * scale[co].
+ *   Ci          a multiple of 4 (as the forward entries), <= 224;  Co 1 .. 224;  any B, D, H, W >= 1
+ *   size limit  B D H W max(Ci, Co) < 2^31: the kernel addresses x, gy and gm by 32-bit element offsets
+ *   workspace   decnet_conv3d_wgrad_workspace_floats(B, D, H, W, Ci, Co) floats (0: shape not covered), 16-byte aligned
+ *               (else DECNET_ERR_MISALIGNED); fewer floats than the query: DECNET_ERR_BAD_SHAPE
+ * Every other buffer is accepted at any float alignment.  The GEMM [Co x voxels] . [voxels x (27 Ci + 1)] runs on
+ * v_mfma_f32_16x16x4_f32 (an fp32 fma chain; no bf16 split).  Deterministic: partition and order are functions of the shape
+ * alone.  The V = B D H W voxels of the flat volume are cut into nsets = ceil(V / sl) slices of sl consecutive voxels (the
+ * last one shorter), sl a power of two: 4096, halved down to 256 while ceil((27 Ci + 1) / 64) * ceil(V / sl) < 1024.  Each
+ * slice is one partial set [Co][27 Ci + 1] of the workspace (the query is exactly nsets * Co * (27 Ci + 1)), an fp32 chain of
+ * sl <= 4096 terms per element; a last launch adds the sets in a fixed order in float64 and rounds once.  No atomics, no
+ * allocation, no synchronisation (capturable); the bits depend neither on a pointer's alignment nor on what LDS held.
+ * NULL (also y without gm): DECNET_ERR_NULL_POINTER; a dimension < 1: DECNET_ERR_BAD_SHAPE; Ci % 4 != 0, Ci or Co > 224,
+ * the size limit: DECNET_ERR_UNSUPPORTED.  Nothing is launched on any refusal. */
+size_t decnet_conv3d_wgrad_workspace_floats(int B, int D, int H, int W, int Ci, int Co);
+int decnet_conv3d_wgrad(const float *x, const float *gy, const float *y, float *gm, float *G, float *gsum,
+                        float *workspace, size_t workspace_floats, int B, int D, int H, int W, int Ci, int Co,
+                        void *stream);
 /* Refinement.get_warped_feats_by_homgrp (submodule.py:719-745): out[b,c,y,x] = bilinear(right[b,c];
  * (x - disp[b,y,x]) * W/(W-1) - 0.5, y * H/(H-1) - 0.5), zero padding.  right,out [B,C,H,W], disp [B,H,W]. */
 int decnet_warp_disparity(const float *right, const float *disp, float *out, int B, int C, int H, int W,
