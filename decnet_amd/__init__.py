@@ -9,7 +9,8 @@
   weight gradient as a deterministic fp32 matrix-core reduction, dx on the forward kernel with flipped weights; and of
   the full-resolution tail (WarpDisparityFunction, Unfold3CatFunction, DynamicUpsample3Function, SigmoidBlendFunction):
   the inference entries forward, fixed-order gathers backward; and of stage 0 (Conv3dFunction, CostVolumeFunction: the
-  eight Conv3d units of CostRegNetNoDown with frozen BatchNorm3d, the per-layer inference entries forward)
+  eight Conv3d units of CostRegNetNoDown, the per-layer inference entries forward; BatchNorm3d frozen, or in .train()
+  mode on the statistics of the batch: BatchNorm3dActFunction, csrc/batchnorm_cl.hip)
 
 Host side is Python on PyTorch-ROCm (device memory + streams only); all arithmetic runs in
 hand-written HIP kernels behind the C ABI of include/decnet_hip.h.  No CPU fallback.
@@ -25,7 +26,7 @@ from .loss import Loss, StageLossFunction  # noqa: F401
 from .conv2d_grad import Conv2dSmallFunction, hip_grad, hip_grad_enabled  # noqa: F401
 from .tail_grad import (DynamicUpsample3Function, SigmoidBlendFunction, Unfold3CatFunction,  # noqa: F401
                         WarpDisparityFunction)
-from .stage0_grad import Conv3dFunction, CostVolumeFunction  # noqa: F401
+from .stage0_grad import BatchNorm3dActFunction, Conv3dFunction, CostVolumeFunction  # noqa: F401
 from .stage0 import (CostRegNetNoDown, GetCostVolume, Stage0, disparity_regression,  # noqa: F401
                      drop_weight_caches, get_disp_samples)
 
@@ -33,4 +34,5 @@ __all__ = ["SpaMat", "SpaVar", "SpaMatFunction", "SpaVarFunction", "spamatvar_fo
            "GetCostVolume", "CostRegNetNoDown", "disparity_regression", "get_disp_samples",
            "Stage0", "DecnetHipError", "version", "drop_weight_caches", "StereoEngine", "Loss",
            "StageLossFunction", "Conv2dSmallFunction", "hip_grad", "hip_grad_enabled", "WarpDisparityFunction",
-           "Unfold3CatFunction", "DynamicUpsample3Function", "SigmoidBlendFunction", "Conv3dFunction", "CostVolumeFunction"]
+           "Unfold3CatFunction", "DynamicUpsample3Function", "SigmoidBlendFunction", "Conv3dFunction", "CostVolumeFunction",
+           "BatchNorm3dActFunction"]

@@ -108,6 +108,9 @@ SIGNATURES = {
     "decnet_bn_train_workspace_floats": [_I] * 4,
     "decnet_bn_train_forward": [_P] * 3 + [_D, _D] + [_P] * 4 + [_I, _P, _Z] + [_I] * 4 + [_P],
     "decnet_bn_train_backward": [_P] * 8 + [_I, _P, _Z] + [_I] * 4 + [_P],
+    "decnet_bn_train_cl_workspace_floats": [_Z, _I],
+    "decnet_bn_train_cl_forward": [_P] * 3 + [_D, _D] + [_P] * 4 + [_I, _P, _Z] + [_Z, _I] + [_P],
+    "decnet_bn_train_cl_backward": [_P] * 8 + [_I, _P, _Z] + [_Z, _I] + [_P],
 }
 
 

@@ -29,8 +29,8 @@ with the 1 x 1 convolutions on decnet_conv2d_mfma_cat_bn_act.
 A unit in ``.train()`` mode (``Unit._forward_grad_train``) runs the same conv Function with scale 1, shift 0 and no ReLU,
 then ``BatchNormActFunction``: BatchNorm2d on the statistics of the batch (+ ReLU), forward and backward on
 csrc/batchnorm.hip, the running statistics updated in place by the forward kernel.
-Stage 0 (Conv3d units, frozen BatchNorm3d) has its own Functions in stage0_grad.py.
-Out of scope: training-mode BatchNorm3d, statistics synchronised across GPUs, ``momentum=None``, the ASPP tap-conv block, the
+Stage 0 (Conv3d units, BatchNorm3d frozen or on the statistics of the batch) has its own Functions in stage0_grad.py.
+Out of scope: statistics synchronised across GPUs, ``momentum=None``, the ASPP tap-conv block, the
 20 x 36 stride-1 layers, double backward.
 """
 import contextlib

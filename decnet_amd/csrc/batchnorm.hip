@@ -17,11 +17,12 @@
 // of a plane (all accesses are single floats) nor on eager versus replay.
 //
 // The pivot p_c = z[0,c,0,0] keeps a channel whose mean is far above its spread from cancelling in S2 / N - (S1 / N)^2.
-// z - mean is formed in float64 (mean is never rounded to fp32); the pre-activation is ONE function, contraction pinned,
-// that forward and backward both call, so the backward's ReLU decision is the forward's on every element and y is not
+// z - mean is formed in float64 (mean is never rounded to fp32); the pre-activation is ONE function (bn_pre.h), contraction
+// pinned, that forward and backward both call, so the backward's ReLU decision is the forward's on every element and y is not
 // read again.
 //
 // This file is built WITHOUT -fno-honor-nans: a NaN in a channel has to reach that channel's statistics and no other's.
+#include "bn_pre.h"
 #include "common.h"
 
 namespace {
@@ -36,13 +37,6 @@ inline unsigned bn_grid(size_t segs) {
 }
 
 inline int bn_nseg(int H, int W) { return (int)(((size_t)H * W + SEG - 1) / SEG); }
-
-// the pre-activation fma(z - mean, a, beta): z - mean in float64, rounded once; no contraction beyond the explicit fma
-__device__ __forceinline__ float bn_pre(float z, double mean, float a, float beta) {
-#pragma clang fp contract(off)
-    const float d = (float)((double)z - mean);
-    return fmaf(d, a, beta);
-}
 
 // segment g of the B C nseg segments: its channel, its first element, its length and its slot among the channel's partials
 struct Segment {

@@ -28,6 +28,7 @@ from ._lib import DecnetHipError, UNSUPPORTED
 from .ops import spamatvar_forward, spamatvar_forward_bits
 from .stage0 import (CachesWeights, CostRegNetNoDown, Stage0, cache_attrs, drop_weight_caches, fold_bn, fold_none,  # noqa: F401
                      source_hold, source_key)
+from .stage0_grad import bn_train_refusal
 
 
 # bench.py's end-to-end accounting: a list that every Unit launch appends (kernel family, algorithmic flops, algorithmic
@@ -291,7 +292,7 @@ class Unit(CachesWeights, nn.Module):
         _grad_route_s3, with their measured exclusions -- less the units measured slower than the library in train mode
         (_bn_train_slower).  Pure, like _route."""
         bn = self.bn
-        if bn is None or not bn.affine or not bn.track_running_stats or not isinstance(bn.momentum, float):
+        if bn is None or bn_train_refusal(bn) is not None:
             return None
         route = self._grad_route_any(B, H, W, parts)
         c = self.conv

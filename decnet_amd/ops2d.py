@@ -233,6 +233,53 @@ def bn_train_backward(z, gy, weight, bias, stats, relu, want_gz=True):
     return gz, dw, db
 
 
+# ---- the same on channels-last volumes: the Conv3d units of stage 0 (csrc/batchnorm_cl.hip; the Function is in stage0_grad.py)
+BN_CL_ROWS = 32                    # DECNET_BN_CL_ROWS of include/decnet_hip.h: rows of a segment, one thread's partial sum
+
+
+def _bn_train_cl_args(z, weight, bias):
+    """z [..., C] (contiguous: a matrix [rows, C]) -> (rows, C), a workspace, its floats."""
+    if _chk("z", z).dim() < 2:
+        raise ValueError("z must be channels-last [..., C] with two dimensions or more, got %s" % (tuple(z.shape),))
+    C = int(z.shape[-1])
+    rows = z.numel() // C if C else 0
+    _chk("weight", weight, (C,))
+    _chk("bias", bias, (C,))
+    nws = int(size("bn_train_cl_workspace_floats", rows, C))              # 0: a shape the entry refuses (it says which)
+    ws = torch.empty(max(nws, 2), dtype=_F32, device=z.device)           # torch allocations are 16-byte aligned
+    return (rows, C), ws, nws
+
+
+def bn_train_cl_forward(z, weight, bias, eps, momentum, running_mean, running_var, relu):
+    """Batch-statistics BatchNorm (+ ReLU) of a channels-last z [..., C] -> (y, stats [2C] float64: {mean, invstd} per
+    channel, what bn_train_cl_backward reads).  running_mean / running_var: both None, or both [C], updated in place.  The
+    workspace comes from torch.empty per call, its size from the library's query."""
+    dims, ws, nws = _bn_train_cl_args(z, weight, bias)
+    if (running_mean is None) != (running_var is None):
+        raise ValueError("running_mean and running_var go together")
+    stats = torch.empty(2 * dims[1], dtype=torch.float64, device=z.device)
+    y = torch.empty_like(z)
+    _call("decnet_bn_train_cl_forward", z, z.data_ptr(), weight.data_ptr(), bias.data_ptr(), float(eps), float(momentum),
+          _opt("running_mean", running_mean, (dims[1],)), _opt("running_var", running_var, (dims[1],)), stats.data_ptr(),
+          y.data_ptr(), 1 if relu else 0, ws.data_ptr(), nws, *dims)
+    return y, stats
+
+
+def bn_train_cl_backward(z, gy, weight, bias, stats, relu, want_gz=True):
+    """-> (gz [..., C] or None, dweight [C], dbias [C]); the ReLU decision is recomputed from z, as the forward made it."""
+    dims, ws, nws = _bn_train_cl_args(z, weight, bias)
+    _chk("gy", gy, z.shape)
+    if not (isinstance(stats, torch.Tensor) and stats.is_cuda and stats.dtype is torch.float64 and stats.is_contiguous() and
+            stats.shape == (2 * dims[1],)):
+        raise TypeError("stats must be the contiguous float64 [2 C] tensor of bn_train_cl_forward, on the GPU")
+    gz = torch.empty_like(z) if want_gz else None
+    dw, db = torch.empty_like(weight), torch.empty_like(bias)
+    _call("decnet_bn_train_cl_backward", z, z.data_ptr(), gy.data_ptr(), weight.data_ptr(), bias.data_ptr(),
+          stats.data_ptr(), gz.data_ptr() if want_gz else None, dw.data_ptr(), db.data_ptr(), 1 if relu else 0,
+          ws.data_ptr(), nws, *dims)
+    return gz, dw, db
+
+
 def bias_act_inplace(x, b, relu):
     B, Co, H, W = _chk("x", x).shape
     _call("decnet_bias_act_inplace", x, x.data_ptr(), _chk("bias", b, (Co,)).data_ptr(), B, Co, H, W, relu)

@@ -10,11 +10,13 @@ reference loads unchanged.  Activations between the HIP kernels are channels-las
 [B,D,H,W,C]; tensors handed back to callers have the reference's logical shapes
 ([B,C,D,H,W] cost volume is returned as a permuted view of the channels-last buffer).
 
-Eval mode only (the reference's training path through these modules is not runnable as shipped).
-Under ``torch.no_grad()`` this is the inference hot path.  Inside ``decnet_amd.hip_grad()``, with autograd on and an input
-or a parameter that requires grad, ``CostRegNetNoDown`` records its backward unit by unit (``_units_grad``,
-stage0_grad.py): gradients of the feature maps, the eight ``conv.weight`` and the BatchNorm weights and biases, with the
-running statistics frozen.  Training-mode BatchNorm3d and cost_func "cat" stay refused under grad.
+Under ``torch.no_grad()`` in eval mode this is the inference hot path.  Inside ``decnet_amd.hip_grad()``, with autograd on
+and an input or a parameter that requires grad, ``CostRegNetNoDown`` records its backward unit by unit (``_units_grad``,
+stage0_grad.py): gradients of the feature maps, the eight ``conv.weight`` and the BatchNorm weights and biases.  In eval
+mode the running statistics are frozen; in ``.train()`` mode (GPU tensors, ``hip_grad()`` on, a gradient wanted) every
+unit whose ``bn`` is in train mode normalises with the statistics of the batch and updates the running ones, as the
+reference's Conv3dUnit.forward does (submodule.py:115-123).  Every other call in ``.train()`` mode and cost_func "cat"
+under grad stay refused.
 """
 import os
 
@@ -176,6 +178,16 @@ def _conv3d_grad_slower(C, voxels):
     eager, one run (tools/bench_stage0_grad.py, profiles/stage0_grad.json).  The measured pairs, hip / library ms, C = 216 on
     20 x 36 x 8: 216 -> 216 1.20 / 6.99 at 23 040 voxels and 2.21 / 13.07 at 46 080; 216 -> 1 0.49 / 4.41 and 0.54 / 8.25.
     None is slower, and nothing is routed at a size nobody measured: every unit stays on the HIP Function."""
+    return False
+
+
+def _conv3d_bn_train_slower(Ci, Co, voxels):
+    """The same for a unit in ``.train()`` mode (Conv3dFunction, then BatchNorm3dActFunction, against
+    ``stage0_grad.unit_library_train``: conv3d -> batch_norm on the statistics of the batch -> ReLU under torch's
+    autograd), forward + backward, eager, one run (tools/bench_stage0_bn_train.py, profiles/stage0_bn_train.json).  The
+    measured pairs, hip / library ms, C = 216 on 20 x 36 x 8: 216 -> 216 1.22 / 6.96 at 23 040 voxels and 2.27 / 12.98 at
+    46 080; 216 -> 1 0.40 / 4.41 and 0.60 / 8.29.  None is slower, and nothing is routed at a size nobody measured: every
+    unit stays on the HIP Functions."""
     return False
 
 
@@ -432,13 +444,18 @@ class CostRegNetNoDown(CachesWeights, nn.Module):
         reg, _ = self.run_ndhwc(_to_ndhwc(x), want_reg=True, want_pred=False)
         return reg
 
-    # ---- the grad path (hip_grad(), eval mode): one Conv3dFunction per unit, stage0_grad.py -----------------------------
+    # ---- the grad path (hip_grad()): one Conv3dFunction per unit (+ BatchNorm3dActFunction in train mode), stage0_grad.py
     def _grad_mode(self, *inputs):
-        """Whether this call records a backward: eval mode, inside ``hip_grad()``, autograd on, and an input or a parameter
-        requires grad.  Raises where a gradient is asked for and cannot be had."""
+        """Whether this call records a backward: inside ``hip_grad()``, autograd on, and an input or a parameter requires
+        grad -- in ``.train()`` mode also: the inputs on the GPU, and every other call is refused.  Raises where a gradient
+        is asked for and cannot be had."""
         if self.training:
-            raise NotImplementedError("CostRegNetNoDown on gfx950 runs in eval mode only (frozen BatchNorm3d; training-mode "
-                                      "BatchNorm3d is not implemented): call .eval()")
+            if hip_grad_enabled() and torch.is_grad_enabled() and all(t.is_cuda for t in inputs) and (
+                    any(t.requires_grad for t in inputs) or any(p.requires_grad for p in self.parameters())):
+                return True
+            raise NotImplementedError("CostRegNetNoDown on gfx950 runs in .train() mode (BatchNorm3d on the statistics of the "
+                                      "batch) only inside decnet_amd.hip_grad(), on GPU tensors, with autograd on and an "
+                                      "input or a parameter that requires grad; for inference call .eval()")
         if not torch.is_grad_enabled():
             return False
         if hip_grad_enabled():
@@ -457,11 +474,30 @@ class CostRegNetNoDown(CachesWeights, nn.Module):
         return [stage0_grad.unit_operands(u.conv.weight.detach().float().contiguous(), variant, last=(i == 7))
                 for i, u in enumerate(self.units())]
 
+    def _unit_train(self, u, packed, x, voxels):
+        """One unit whose ``bn`` is in ``.train()`` mode, on x [B,D,H,W,Ci] -> y [B,D,H,W,Co]: z = conv(x, w) as
+        Conv3dFunction with scale 1, shift 0 and no ReLU (no y saved; its backward launches the weight gradient for dW
+        alone, and dx on the flipped weights), then BatchNorm3dActFunction on the statistics of the batch, which also
+        updates the running statistics; ``num_batches_tracked`` is counted here."""
+        bn, w = u.bn, u.conv.weight
+        Co = int(w.shape[0])
+        if _conv3d_bn_train_slower(int(w.shape[1]), Co, voxels):
+            y = stage0_grad.unit_library_train(x, w, bn, bool(u.relu))
+        else:
+            z = stage0_grad.Conv3dFunction.apply(packed, False, w, torch.ones(Co, device=x.device),
+                                                 torch.zeros(Co, device=x.device), x)
+            y = stage0_grad.BatchNorm3dActFunction.apply(z, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps,
+                                                         bn.momentum, bool(u.relu))
+        with torch.no_grad():
+            bn.num_batches_tracked.add_(1)
+        return y
+
     def _units_grad(self, x):
         """The eight units on a channels-last volume x [B,D,H,W,C] under autograd -> [y0 .. y6, reg]: every unit's output
         ([B,D,H,W,C]; reg [B,D,H,W,1]), y4 before the residual is added (so that y_i > 0 is unit i's ReLU mask).  The
         forward operands are packed from the weights alone and cached like ``prepare()``'s; scale and shift are
-        differentiable expressions of the BatchNorm parameters, formed per call."""
+        differentiable expressions of the BatchNorm parameters, formed per call.  A unit whose ``bn`` is in ``.train()``
+        mode goes through ``_unit_train``, unit by unit; one whose ``bn`` is in eval mode keeps the frozen route."""
         if self.cost_func == "cat":
             raise NotImplementedError(stage0_grad._REFUSED % "cat")
         units = self.units()
@@ -479,13 +515,21 @@ class CostRegNetNoDown(CachesWeights, nn.Module):
         ws = None
         if variant is not None:
             ws = self._grow(("wino", x.device), ops2d.size("conv3d_wino_workspace_floats", B, D, H, W, C, C, variant))
+        for i, u in enumerate(units):                        # refused before any unit has written a running statistic
+            why = stage0_grad.bn_train_refusal(u.bn) if u.bn.training else None
+            if why is not None:
+                raise NotImplementedError("training-mode BatchNorm3d under hip_grad() takes an affine BatchNorm3d that tracks "
+                                          "its running statistics with a float momentum; unit %d has %s" % (i, why))
         outs, cur, keep = [], x, None
         for i, u in enumerate(units):
-            scale, shift = fold_bn(u.bn)
-            if _conv3d_grad_slower(C, B * D * H * W):
-                y = stage0_grad.unit_library(cur, u.conv.weight, scale, shift, bool(u.relu))
+            if u.bn.training:                                # the statistics of the batch; a frozen bn stays on its route
+                y = self._unit_train(u, dict(P[i], ws=ws), cur, B * D * H * W)
             else:
-                y = stage0_grad.Conv3dFunction.apply(dict(P[i], ws=ws), bool(u.relu), u.conv.weight, scale, shift, cur)
+                scale, shift = fold_bn(u.bn)
+                if _conv3d_grad_slower(C, B * D * H * W):
+                    y = stage0_grad.unit_library(cur, u.conv.weight, scale, shift, bool(u.relu))
+                else:
+                    y = stage0_grad.Conv3dFunction.apply(dict(P[i], ws=ws), bool(u.relu), u.conv.weight, scale, shift, cur)
             outs.append(y)
             cur = y + keep if i == 4 else y                  # conv1(output0) + output0, after the ReLU
             if i == 1:

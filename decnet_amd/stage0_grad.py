@@ -17,8 +17,14 @@ forward is the per-layer inference entry -- decnet_conv3d_wino_bn_act, decnet_co
 unit decnet_conv3d_cout1_softargmax -- so y has the bits of the ``no_grad`` per-layer forward.  The fused Winograd stack
 and decnet_stage0_forward_cf keep the activations on chip and are never taken under grad.
 
+A unit whose ``bn`` is in ``.train()`` mode runs as ``Conv3dFunction`` with scale 1, shift 0 and no ReLU (z = conv(x, w):
+no y saved, the weight gradient launched for dW alone, dx on the flipped weights), then ``BatchNorm3dActFunction``:
+BatchNorm on the statistics of the batch (+ ReLU) on the channels-last volume, forward and backward on
+decnet_bn_train_cl_forward / _backward (csrc/batchnorm_cl.hip), which also update the running statistics.
+
 ``CostVolumeFunction`` is decnet_costvol_forward_cf forward; its backward differentiates a torch restatement of the
-header's formula.  Out of scope: training-mode BatchNorm3d, cost_func "cat", a bf16x3 weight gradient, double backward.
+header's formula.  Out of scope: cost_func "cat", a bf16x3 weight gradient, double backward, statistics synchronised across
+GPUs, ``momentum=None``.
 """
 import torch
 from torch.autograd import Function
@@ -138,6 +144,48 @@ class Conv3dFunction(Function):
         return (None, None, dw, dscale, dshift, dx)
 
 
+class BatchNorm3dActFunction(Function):
+    """apply(z, weight, bias, running_mean, running_var, eps, momentum, relu) -> y = act(batch_norm(z)) on the statistics
+    of the batch, z a channels-last volume [B,D,H,W,C] (decnet_bn_train_cl_forward).  Shaped like
+    conv2d_grad.BatchNormActFunction: running_mean / running_var (both None, or both [C]) are written in place by the
+    kernel, which autograd does not see, so their versions are bumped here and the caches that fold the running
+    statistics (stage0.source_key) rebuild on the next eval forward.  ``num_batches_tracked`` is the caller's.  Gradients:
+    z, weight, bias, each only when wanted; the ReLU decision is recomputed from z, y is not saved."""
+
+    @staticmethod
+    def forward(ctx, z, weight, bias, running_mean, running_var, eps, momentum, relu):
+        z = z.contiguous()
+        y, stats = ops2d.bn_train_cl_forward(z, weight, bias, eps, momentum, running_mean, running_var, relu)
+        if running_mean is not None:
+            torch.autograd.graph.increment_version(running_mean)
+            torch.autograd.graph.increment_version(running_var)
+        ctx.relu = bool(relu)
+        ctx.save_for_backward(z, weight, bias, stats)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        z, weight, bias, stats = ctx.saved_tensors
+        need_z, need_w, need_b = ctx.needs_input_grad[:3]
+        gz = dw = db = None
+        if need_z or need_w or need_b:
+            gz, dw, db = ops2d.bn_train_cl_backward(z, gy.contiguous(), weight, bias, stats, ctx.relu, want_gz=need_z)
+        return (gz, dw if need_w else None, db if need_b else None, None, None, None, None, None)
+
+
+def bn_train_refusal(bn):
+    """Why a BatchNorm in ``.train()`` mode cannot run on the statistics of the batch under ``hip_grad()`` (the condition of
+    model.Unit._grad_route_train), or None."""
+    if not bn.affine:
+        return "affine=False"
+    if not bn.track_running_stats:
+        return "track_running_stats=False"
+    if not isinstance(bn.momentum, float):
+        return "momentum=%r (a cumulative average)" % (bn.momentum,)
+    return None
+
+
 _REFUSED = ("the gradient of stage 0 covers cost_func 'cor' and 'ssd'; '%s' (the 2C-channel volume behind conv_pre) is "
             "refused under grad")
 
@@ -209,4 +257,13 @@ def unit_library(x, w, scale, shift, relu):
     * scale + shift and ReLU, under autograd -> [B,D,H,W,Co]."""
     y = torch.nn.functional.conv3d(x.permute(0, 4, 1, 2, 3), w, None, stride=1, padding=1).permute(0, 2, 3, 4, 1)
     y = y * scale + shift
+    return torch.relu(y) if relu else y
+
+
+def unit_library_train(x, w, bn, relu):
+    """The library arm of one unit in ``.train()`` mode: torch's conv3d, then torch's batch_norm on the statistics of the
+    batch (it updates bn's running statistics; ``num_batches_tracked`` is the caller's) and ReLU -> [B,D,H,W,Co]."""
+    z = torch.nn.functional.conv3d(x.permute(0, 4, 1, 2, 3), w, None, stride=1, padding=1)
+    y = torch.nn.functional.batch_norm(z, bn.running_mean, bn.running_var, bn.weight, bn.bias, True, bn.momentum, bn.eps)
+    y = y.permute(0, 2, 3, 4, 1)
     return torch.relu(y) if relu else y

@@ -699,6 +699,31 @@ int decnet_bn_train_backward(const float *z, const float *gy, const float *gamma
                              float *gz, float *dgamma, float *dbeta, int relu, void *workspace, size_t workspace_floats,
                              int B, int C, int H, int W, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * The same on a CHANNELS-LAST matrix (csrc/batchnorm_cl.hip): z [rows, C] fp32 at any float alignment, channel c the
+ * column z[:, c], N = rows values per channel -- the Conv3d units of stage 0, whose volumes are [B,D,H,W,C]
+ * (rows = B D H W).  Any C >= 1.  The contract, formulas, roundings, optional arguments and error codes are those of
+ * decnet_bn_train_forward / _backward above, with these differences:
+ *   workspace  decnet_bn_train_cl_workspace_floats(rows, C) floats, 8-byte aligned.  The rows are cut into
+ *              nseg = ceil(rows / DECNET_BN_CL_ROWS) segments of DECNET_BN_CL_ROWS rows; the workspace holds the partial
+ *              sums [nseg][C][2] float64, then [C][2] totals.  The query returns 0 for a shape the entries refuse.
+ *   order      the partial of (segment, channel) is one thread's float64 sum over the segment's rows in rising order;
+ *              a channel's partials are added by 16 threads (thread j: segments j, j + 16, ... in rising order), whose
+ *              sums are added in a fixed tree.  No atomics; the bits depend neither on the launch shape, nor on the
+ *              alignment of any pointer (every access is a single float), nor on eager versus replay.
+ *   pivot      p = z[0, c].
+ * DECNET_ERR_BAD_SHAPE: rows < 2, C < 1, rows C >= 2^31, fewer workspace floats than the query.  Nothing is launched
+ * on any refusal.  Three launches each (the backward two when gz is NULL).
+ * ------------------------------------------------------------------------------------- */
+#define DECNET_BN_CL_ROWS 32
+size_t decnet_bn_train_cl_workspace_floats(size_t rows, int C);
+int decnet_bn_train_cl_forward(const float *z, const float *gamma, const float *beta, double eps, double momentum,
+                               float *running_mean, float *running_var, double *stats, float *y, int relu, void *workspace,
+                               size_t workspace_floats, size_t rows, int C, void *stream);
+int decnet_bn_train_cl_backward(const float *z, const float *gy, const float *gamma, const float *beta, const double *stats,
+                                float *gz, float *dgamma, float *dbeta, int relu, void *workspace, size_t workspace_floats,
+                                size_t rows, int C, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
