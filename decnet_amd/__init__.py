@@ -10,7 +10,7 @@
   the full-resolution tail (WarpDisparityFunction, Unfold3CatFunction, DynamicUpsample3Function, SigmoidBlendFunction):
   the inference entries forward, fixed-order gathers backward; and of stage 0 (Conv3dFunction, CostVolumeFunction: the
   eight Conv3d units of CostRegNetNoDown, the per-layer inference entries forward; BatchNorm3d frozen, or in .train()
-  mode on the statistics of the batch: BatchNorm3dActFunction, csrc/batchnorm_cl.hip)
+  mode on the statistics of the batch: BatchNorm3dActFunction, the Columns layout of csrc/batchnorm.hip)
 
 Host side is Python on PyTorch-ROCm (device memory + streams only); all arithmetic runs in
 hand-written HIP kernels behind the C ABI of include/decnet_hip.h.  No CPU fallback.

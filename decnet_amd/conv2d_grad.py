@@ -238,30 +238,41 @@ class Deconv2dS3Function(Function):
         return (None, None, None, dw, dscale, dshift, dx)
 
 
+def bn_act_forward(bn_forward, ctx, z, weight, bias, running_mean, running_var, eps, momentum, relu):
+    """The forward of BatchNormActFunction and stage0_grad.BatchNorm3dActFunction on their ops2d entry `bn_forward`.  The
+    kernel writes running_mean / running_var in place, which autograd does not see: their versions are bumped here."""
+    z = z.contiguous()
+    y, stats = bn_forward(z, weight, bias, eps, momentum, running_mean, running_var, relu)
+    if running_mean is not None:
+        torch.autograd.graph.increment_version(running_mean)
+        torch.autograd.graph.increment_version(running_var)
+    ctx.relu = bool(relu)
+    ctx.save_for_backward(z, weight, bias, stats)
+    return y
+
+
+def bn_act_backward(bn_backward, ctx, gy):
+    """Their backward: the gradients of z, weight, bias, each only when wanted."""
+    z, weight, bias, stats = ctx.saved_tensors
+    need_z, need_w, need_b = ctx.needs_input_grad[:3]
+    gz = dw = db = None
+    if need_z or need_w or need_b:
+        gz, dw, db = bn_backward(z, gy.contiguous(), weight, bias, stats, ctx.relu, want_gz=need_z)
+    return (gz, dw if need_w else None, db if need_b else None, None, None, None, None, None)
+
+
 class BatchNormActFunction(Function):
     """apply(z, weight, bias, running_mean, running_var, eps, momentum, relu) -> y = act(batch_norm(z)) on the statistics
     of the batch z [B,C,H,W] (decnet_bn_train_forward).  running_mean / running_var (both None, or both [C]) are written in
-    place by the kernel, which autograd does not see: their versions are bumped here, so the caches that fold the running
+    place by the kernel, which autograd does not see: their versions are bumped, so the caches that fold the running
     statistics (stage0.source_key) rebuild on the next eval forward.  ``num_batches_tracked`` is the caller's.  Gradients:
     z, weight, bias, each only when wanted; the ReLU decision is recomputed from z, y is not saved."""
 
     @staticmethod
-    def forward(ctx, z, weight, bias, running_mean, running_var, eps, momentum, relu):
-        z = z.contiguous()
-        y, stats = ops2d.bn_train_forward(z, weight, bias, eps, momentum, running_mean, running_var, relu)
-        if running_mean is not None:
-            torch.autograd.graph.increment_version(running_mean)
-            torch.autograd.graph.increment_version(running_var)
-        ctx.relu = bool(relu)
-        ctx.save_for_backward(z, weight, bias, stats)
-        return y
+    def forward(ctx, *args):
+        return bn_act_forward(ops2d.bn_train_forward, ctx, *args)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        z, weight, bias, stats = ctx.saved_tensors
-        need_z, need_w, need_b = ctx.needs_input_grad[:3]
-        gz = dw = db = None
-        if need_z or need_w or need_b:
-            gz, dw, db = ops2d.bn_train_backward(z, gy.contiguous(), weight, bias, stats, ctx.relu, want_gz=need_z)
-        return (gz, dw if need_w else None, db if need_b else None, None, None, None, None, None)
+        return bn_act_backward(ops2d.bn_train_backward, ctx, gy)

@@ -191,93 +191,75 @@ def deconv2d_k3s3_wgrad(x, gy, y):
     return _wgrad_s3("deconv2d_k3s3_wgrad", True, x, gy, y)
 
 
-# ---- training-mode BatchNorm + ReLU under hip_grad() (csrc/batchnorm.hip; the Function is in conv2d_grad.py) -------------
+# ---- training-mode BatchNorm + ReLU under hip_grad() (csrc/batchnorm.hip) on its two layouts: NCHW planes (the Function
+# is in conv2d_grad.py) and channels-last volumes, the Conv3d units of stage 0 (the Function is in stage0_grad.py) --------
 BN_SEGMENT = 4096                  # DECNET_BN_SEGMENT of include/decnet_hip.h: floats of a plane one wave sums
-
-
-def _bn_train_args(z, weight, bias):
-    B, C, H, W = _chk("z", z).shape
-    _chk("weight", weight, (C,))
-    _chk("bias", bias, (C,))
-    nws = int(size("bn_train_workspace_floats", B, C, H, W))             # 0: a shape the entry refuses (it says which)
-    ws = torch.empty(max(nws, 2), dtype=_F32, device=z.device)           # torch allocations are 16-byte aligned
-    return (B, C, H, W), ws, nws
-
-
-def bn_train_forward(z, weight, bias, eps, momentum, running_mean, running_var, relu):
-    """Batch-statistics BatchNorm2d (+ ReLU) of z [B,C,H,W] -> (y, stats [2C] float64: {mean, invstd} per channel, what
-    bn_train_backward reads).  running_mean / running_var: both None, or both [C], updated in place.  The workspace comes
-    from torch.empty per call, its size from the library's query."""
-    dims, ws, nws = _bn_train_args(z, weight, bias)
-    if (running_mean is None) != (running_var is None):
-        raise ValueError("running_mean and running_var go together")
-    stats = torch.empty(2 * dims[1], dtype=torch.float64, device=z.device)
-    y = torch.empty_like(z)
-    _call("decnet_bn_train_forward", z, z.data_ptr(), weight.data_ptr(), bias.data_ptr(), float(eps), float(momentum),
-          _opt("running_mean", running_mean, (dims[1],)), _opt("running_var", running_var, (dims[1],)), stats.data_ptr(),
-          y.data_ptr(), 1 if relu else 0, ws.data_ptr(), nws, *dims)
-    return y, stats
-
-
-def bn_train_backward(z, gy, weight, bias, stats, relu, want_gz=True):
-    """-> (gz [B,C,H,W] or None, dweight [C], dbias [C]); the ReLU decision is recomputed from z, as the forward made it."""
-    dims, ws, nws = _bn_train_args(z, weight, bias)
-    _chk("gy", gy, z.shape)
-    if not (isinstance(stats, torch.Tensor) and stats.is_cuda and stats.dtype is torch.float64 and stats.is_contiguous() and
-            stats.shape == (2 * dims[1],)):
-        raise TypeError("stats must be the contiguous float64 [2 C] tensor of bn_train_forward, on the GPU")
-    gz = torch.empty_like(z) if want_gz else None
-    dw, db = torch.empty_like(weight), torch.empty_like(bias)
-    _call("decnet_bn_train_backward", z, z.data_ptr(), gy.data_ptr(), weight.data_ptr(), bias.data_ptr(), stats.data_ptr(),
-          gz.data_ptr() if want_gz else None, dw.data_ptr(), db.data_ptr(), 1 if relu else 0, ws.data_ptr(), nws, *dims)
-    return gz, dw, db
-
-
-# ---- the same on channels-last volumes: the Conv3d units of stage 0 (csrc/batchnorm_cl.hip; the Function is in stage0_grad.py)
 BN_CL_ROWS = 32                    # DECNET_BN_CL_ROWS of include/decnet_hip.h: rows of a segment, one thread's partial sum
 
 
-def _bn_train_cl_args(z, weight, bias):
-    """z [..., C] (contiguous: a matrix [rows, C]) -> (rows, C), a workspace, its floats."""
+def _planes_dims(z):
+    B, C, H, W = _chk("z", z).shape
+    return B, C, H, W
+
+
+def _columns_dims(z):
+    """z [..., C] (contiguous: a matrix [rows, C]) -> (rows, C)."""
     if _chk("z", z).dim() < 2:
         raise ValueError("z must be channels-last [..., C] with two dimensions or more, got %s" % (tuple(z.shape),))
     C = int(z.shape[-1])
-    rows = z.numel() // C if C else 0
-    _chk("weight", weight, (C,))
-    _chk("bias", bias, (C,))
-    nws = int(size("bn_train_cl_workspace_floats", rows, C))              # 0: a shape the entry refuses (it says which)
+    return z.numel() // C if C else 0, C
+
+
+# a layout: (z -> the entry's dims, C second; the stem of the public names, of the entries and of the size query)
+_PLANES = (_planes_dims, "bn_train")
+_COLUMNS = (_columns_dims, "bn_train_cl")
+
+
+def _bn_train_args(layout, z, weight, bias):
+    dims = layout[0](z)
+    _chk("weight", weight, (dims[1],))
+    _chk("bias", bias, (dims[1],))
+    nws = int(size(layout[1] + "_workspace_floats", *dims))              # 0: a shape the entry refuses (it says which)
     ws = torch.empty(max(nws, 2), dtype=_F32, device=z.device)           # torch allocations are 16-byte aligned
-    return (rows, C), ws, nws
+    return dims, ws, nws
 
 
-def bn_train_cl_forward(z, weight, bias, eps, momentum, running_mean, running_var, relu):
-    """Batch-statistics BatchNorm (+ ReLU) of a channels-last z [..., C] -> (y, stats [2C] float64: {mean, invstd} per
-    channel, what bn_train_cl_backward reads).  running_mean / running_var: both None, or both [C], updated in place.  The
-    workspace comes from torch.empty per call, its size from the library's query."""
-    dims, ws, nws = _bn_train_cl_args(z, weight, bias)
+def _bn_train_forward(layout, z, weight, bias, eps, momentum, running_mean, running_var, relu):
+    """Batch-statistics BatchNorm (+ ReLU) of z -> (y, stats [2C] float64: {mean, invstd} per channel, what the backward
+    reads).  running_mean / running_var: both None, or both [C], updated in place.  The workspace comes from torch.empty
+    per call, its size from the library's query."""
+    dims, ws, nws = _bn_train_args(layout, z, weight, bias)
     if (running_mean is None) != (running_var is None):
         raise ValueError("running_mean and running_var go together")
     stats = torch.empty(2 * dims[1], dtype=torch.float64, device=z.device)
     y = torch.empty_like(z)
-    _call("decnet_bn_train_cl_forward", z, z.data_ptr(), weight.data_ptr(), bias.data_ptr(), float(eps), float(momentum),
+    _call("decnet_%s_forward" % layout[1], z, z.data_ptr(), weight.data_ptr(), bias.data_ptr(), float(eps), float(momentum),
           _opt("running_mean", running_mean, (dims[1],)), _opt("running_var", running_var, (dims[1],)), stats.data_ptr(),
           y.data_ptr(), 1 if relu else 0, ws.data_ptr(), nws, *dims)
     return y, stats
 
 
-def bn_train_cl_backward(z, gy, weight, bias, stats, relu, want_gz=True):
-    """-> (gz [..., C] or None, dweight [C], dbias [C]); the ReLU decision is recomputed from z, as the forward made it."""
-    dims, ws, nws = _bn_train_cl_args(z, weight, bias)
+def _bn_train_backward(layout, z, gy, weight, bias, stats, relu, want_gz=True):
+    """-> (gz like z or None, dweight [C], dbias [C]); the ReLU decision is recomputed from z, as the forward made it."""
+    dims, ws, nws = _bn_train_args(layout, z, weight, bias)
     _chk("gy", gy, z.shape)
     if not (isinstance(stats, torch.Tensor) and stats.is_cuda and stats.dtype is torch.float64 and stats.is_contiguous() and
             stats.shape == (2 * dims[1],)):
-        raise TypeError("stats must be the contiguous float64 [2 C] tensor of bn_train_cl_forward, on the GPU")
+        raise TypeError("stats must be the contiguous float64 [2 C] tensor of %s_forward, on the GPU" % layout[1])
     gz = torch.empty_like(z) if want_gz else None
     dw, db = torch.empty_like(weight), torch.empty_like(bias)
-    _call("decnet_bn_train_cl_backward", z, z.data_ptr(), gy.data_ptr(), weight.data_ptr(), bias.data_ptr(),
+    _call("decnet_%s_backward" % layout[1], z, z.data_ptr(), gy.data_ptr(), weight.data_ptr(), bias.data_ptr(),
           stats.data_ptr(), gz.data_ptr() if want_gz else None, dw.data_ptr(), db.data_ptr(), 1 if relu else 0,
           ws.data_ptr(), nws, *dims)
     return gz, dw, db
+
+
+# (z, weight, bias, eps, momentum, running_mean, running_var, relu) / (z, gy, weight, bias, stats, relu, want_gz=True);
+# z [B,C,H,W], or with _cl a channels-last [..., C]
+bn_train_forward = partial(_bn_train_forward, _PLANES)
+bn_train_backward = partial(_bn_train_backward, _PLANES)
+bn_train_cl_forward = partial(_bn_train_forward, _COLUMNS)
+bn_train_cl_backward = partial(_bn_train_backward, _COLUMNS)
 
 
 def bias_act_inplace(x, b, relu):

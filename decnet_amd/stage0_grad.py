@@ -20,7 +20,7 @@ and decnet_stage0_forward_cf keep the activations on chip and are never taken un
 A unit whose ``bn`` is in ``.train()`` mode runs as ``Conv3dFunction`` with scale 1, shift 0 and no ReLU (z = conv(x, w):
 no y saved, the weight gradient launched for dW alone, dx on the flipped weights), then ``BatchNorm3dActFunction``:
 BatchNorm on the statistics of the batch (+ ReLU) on the channels-last volume, forward and backward on
-decnet_bn_train_cl_forward / _backward (csrc/batchnorm_cl.hip), which also update the running statistics.
+decnet_bn_train_cl_forward / _backward (csrc/batchnorm.hip, the Columns layout), which also update the running statistics.
 
 ``CostVolumeFunction`` is decnet_costvol_forward_cf forward; its backward differentiates a torch restatement of the
 header's formula.  Out of scope: cost_func "cat", a bf16x3 weight gradient, double backward, statistics synchronised across
@@ -31,6 +31,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import ops2d
+from .conv2d_grad import bn_act_backward, bn_act_forward
 
 
 def flipped_weight3d(w, scale):
@@ -146,32 +147,17 @@ class Conv3dFunction(Function):
 
 class BatchNorm3dActFunction(Function):
     """apply(z, weight, bias, running_mean, running_var, eps, momentum, relu) -> y = act(batch_norm(z)) on the statistics
-    of the batch, z a channels-last volume [B,D,H,W,C] (decnet_bn_train_cl_forward).  Shaped like
-    conv2d_grad.BatchNormActFunction: running_mean / running_var (both None, or both [C]) are written in place by the
-    kernel, which autograd does not see, so their versions are bumped here and the caches that fold the running
-    statistics (stage0.source_key) rebuild on the next eval forward.  ``num_batches_tracked`` is the caller's.  Gradients:
-    z, weight, bias, each only when wanted; the ReLU decision is recomputed from z, y is not saved."""
+    of the batch, z a channels-last volume [B,D,H,W,C] (decnet_bn_train_cl_forward): conv2d_grad.BatchNormActFunction on
+    the other layout, one body (conv2d_grad.bn_act_forward / bn_act_backward)."""
 
     @staticmethod
-    def forward(ctx, z, weight, bias, running_mean, running_var, eps, momentum, relu):
-        z = z.contiguous()
-        y, stats = ops2d.bn_train_cl_forward(z, weight, bias, eps, momentum, running_mean, running_var, relu)
-        if running_mean is not None:
-            torch.autograd.graph.increment_version(running_mean)
-            torch.autograd.graph.increment_version(running_var)
-        ctx.relu = bool(relu)
-        ctx.save_for_backward(z, weight, bias, stats)
-        return y
+    def forward(ctx, *args):
+        return bn_act_forward(ops2d.bn_train_cl_forward, ctx, *args)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        z, weight, bias, stats = ctx.saved_tensors
-        need_z, need_w, need_b = ctx.needs_input_grad[:3]
-        gz = dw = db = None
-        if need_z or need_w or need_b:
-            gz, dw, db = ops2d.bn_train_cl_backward(z, gy.contiguous(), weight, bias, stats, ctx.relu, want_gz=need_z)
-        return (gz, dw if need_w else None, db if need_b else None, None, None, None, None, None)
+        return bn_act_backward(ops2d.bn_train_cl_backward, ctx, gy)
 
 
 def bn_train_refusal(bn):

@@ -700,9 +700,9 @@ int decnet_bn_train_backward(const float *z, const float *gy, const float *gamma
                              int B, int C, int H, int W, void *stream);
 
 /* ---------------------------------------------------------------------------------------
- * The same on a CHANNELS-LAST matrix (csrc/batchnorm_cl.hip): z [rows, C] fp32 at any float alignment, channel c the
- * column z[:, c], N = rows values per channel -- the Conv3d units of stage 0, whose volumes are [B,D,H,W,C]
- * (rows = B D H W).  Any C >= 1.  The contract, formulas, roundings, optional arguments and error codes are those of
+ * The same on a CHANNELS-LAST matrix (csrc/batchnorm.hip, its Columns layout): z [rows, C] fp32 at any float alignment,
+ * channel c the column z[:, c], N = rows values per channel -- the Conv3d units of stage 0, whose volumes are
+ * [B,D,H,W,C] (rows = B D H W).  Any C >= 1.  The contract, formulas, roundings, optional arguments and error codes are those of
  * decnet_bn_train_forward / _backward above, with these differences:
  *   workspace  decnet_bn_train_cl_workspace_floats(rows, C) floats, 8-byte aligned.  The rows are cut into
  *              nseg = ceil(rows / DECNET_BN_CL_ROWS) segments of DECNET_BN_CL_ROWS rows; the workspace holds the partial

@@ -1,7 +1,7 @@
 """Float64 restatement of training-mode BatchNorm2d (+ ReLU), forward and backward (decnet_amd/csrc/batchnorm.hip,
 conv2d_grad.BatchNormActFunction), the data sets of its tests, and the seeded unit and module cases of
-tests/test_bn_train_gpu.py.  CPU only; a helper module of tests/test_bn_train_cpu.py (which holds it against torch's own
-float64 autograd) and of the GPU test.
+tests/test_bn_train_gpu.py, and `check_entry`, the bounds both GPU files hold the entries to.  CPU only; a helper
+module of tests/test_bn_train_cpu.py (which holds it against torch's own float64 autograd) and of the GPU tests.
 
 For z [B,C,H,W], N = B H W values per channel, the pivot p_c = z[0,c,0,0]:
     mean = p + sum (z - p) / N,  var = sum (z - mean)^2 / N (biased),  invstd = 1 / sqrt(var + eps),  xhat = (z - mean) invstd
@@ -64,6 +64,57 @@ def backward(fwd, gy, gamma, relu=True, mask=None):
     gz = _pc(gamma * fwd["invstd"]) * (gm - _pc(dbeta) / n - xhat * _pc(dgamma) / n)
     return dict(gm=gm, gz=gz, dgamma=dgamma, dbeta=dbeta, abs_dgamma=(gm * xhat).abs().sum((0, 2, 3)),
                 abs_dbeta=gm.abs().sum((0, 2, 3)))
+
+
+def check_entry(r, f, gamma, beta, gy, relu, eps, tag, buffers=True):
+    """The bounds of the entries' results r (y and gz in the NCHW view) against f, the float64 forward of the same z, each
+    from counting roundings with a margin of a small factor (u = 2^-24):
+      statistics   |mean - mean64| <= 2^-40 mean|z - p|; |var - var64| <= 2^-40 mean (z - p)^2 + 16 x 2^-53 (var64 + eps), var taken
+                   back out of the kernel's invstd as 1 / invstd^2 - eps -- the second term: eight float64 roundings of at
+                   most 2^-53 (var + eps) each (the sum var + eps, the square root and the division in the kernel, the
+                   last two twice in invstd^2; the square, the division and the subtraction here), margin 2; and through
+                   invstd = (var + eps)^-1/2 itself, whose derivative carries
+                   |var - var64| <= 2^-40 mean (z - p)^2 to |invstd - invstd64| <= invstd64 (2^-41 mean (z - p)^2 / (var64 + eps)
+                   + 4 x 2^-53) -- the second term: the square root and the division in float64 -- so that a constant channel
+                   (var = 0 exactly) is held to the roundings of 1 / sqrt(eps) alone;
+      buffers      2 u relative;
+      output       4 u (|xhat64 gamma| + |beta|) + |a| |mean - mean64|;
+      dgamma       4 u sum |gm xhat|, dbeta 2 u sum |gm|, gz 8 u |a| (|gm| + |dbeta| / N + |xhat| |dgamma| / N), the mask [y_gpu > 0]
+                   imposed, every imposed decision that is not float64's own within the output bound of zero."""
+    U = U32
+    n = f["xhat"].numel() // f["xhat"].shape[1]
+    mean, invstd = r["stats"][0::2], r["stats"][1::2]
+    e_mean = (mean - f["mean"]).abs()
+    assert bool((e_mean <= 2.0 ** -40 * f["dev1"]).all()), ("mean", e_mean, f["dev1"])
+    b_inv = f["invstd"] * (2.0 ** -41 * f["dev2"] / (f["var"] + eps) + 4 * 2.0 ** -53)
+    assert bool(((invstd - f["invstd"]).abs() <= b_inv).all()), ("invstd", invstd - f["invstd"], b_inv)
+    var = 1.0 / (invstd * invstd) - eps                       # the kernel's var back out of invstd, in float64
+    b_var = 2.0 ** -40 * f["dev2"] + 16 * 2.0 ** -53 * (f["var"] + eps)
+    assert bool(((var - f["var"]).abs() <= b_var).all()), ("var", var - f["var"], b_var)
+    if buffers:
+        for k in ("running_mean", "running_var"):
+            assert bool(((r[k].double() - f[k]).abs() <= 2 * U * f[k].abs()).all()), k
+    g64 = gamma.double()
+    a = (g64 * f["invstd"]).abs()
+    b_y = 4 * U * ((f["xhat"] * _pc(g64)).abs() + _pc(beta.double().abs())) + _pc(a * e_mean)
+    e_y = (r["y"].double() - f["y"]).abs()
+    print(tag, "y: worst error / bound = %.3g" % float((e_y / b_y.clamp_min(1e-300)).max()))
+    assert bool((e_y <= b_y).all()), "y"
+    mask = None
+    if relu:
+        mask = r["y"] > 0
+        flipped = mask != (f["pre"] > 0)
+        assert bool((f["pre"].abs()[flipped] <= b_y[flipped]).all()), "a ReLU decision far from zero differs from float64's"
+    g = backward(f, gy, gamma, relu, mask)
+    for k, factor in (("dgamma", 4), ("dbeta", 2)):
+        err, bound = (r[k].double() - g[k]).abs(), factor * U * g["abs_" + k]
+        print(tag, k, "worst error / bound = %.3g" % float((err / bound.clamp_min(1e-300)).max()))
+        assert bool((err <= bound).all()), (k, err, bound)
+    b_gz = 8 * U * _pc(a) * (g["gm"].abs() + _pc(g["dbeta"].abs()) / n + f["xhat"].abs() * _pc(g["dgamma"].abs()) / n)
+    e_gz = (r["gz"].double() - g["gz"]).abs()
+    print(tag, "gz: worst error / bound = %.3g" % float((e_gz / b_gz.clamp_min(1e-300)).max()))
+    assert bool((e_gz <= b_gz).all()), "gz"
+    assert not any(bool(torch.isnan(v).any()) for v in r.values())
 
 
 # ---- the data sets of the entry tests ------------------------------------------------------------------------------------------

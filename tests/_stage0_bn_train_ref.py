@@ -1,4 +1,4 @@
-"""Float64 references of training-mode BatchNorm3d in stage 0 (decnet_amd/csrc/batchnorm_cl.hip,
+"""Float64 references of training-mode BatchNorm3d in stage 0 (decnet_amd/csrc/batchnorm.hip, the Columns layout,
 stage0_grad.BatchNorm3dActFunction, CostRegNetNoDown in .train() mode under hip_grad()) for
 tests/test_stage0_bn_train_cpu.py and tests/test_stage0_bn_train_gpu.py.  CPU only.
 
@@ -18,7 +18,7 @@ import _stage0_grad_ref as SG
 
 F64 = torch.float64
 ROWS = 32                                   # DECNET_BN_CL_ROWS of include/decnet_hip.h: rows of a segment
-FIN_J = 16                                  # csrc/batchnorm_cl.hip: the finish kernel's threads per channel (16 x 16 channels)
+FIN_J = 16                                  # csrc/batchnorm.hip, Columns: the finish kernel's threads per channel (of 16)
 FIN_THREADS = 256                           # ... and of its workgroup
 
 

@@ -1,7 +1,7 @@
 """Training-mode BatchNorm under hip_grad() on the GPU (csrc/batchnorm.hip, conv2d_grad.BatchNormActFunction,
 Unit._forward_grad_train) against the float64 restatement of tests/_bn_train_ref.py:
   1. decnet_bn_train_forward / _backward through the C ABI at the edge shapes, at both placements and under both LDS poison
-     words (tests/_placement._both), every bound counted from roundings (u = 2^-24; see _check_entry);
+     words (tests/_placement._both), every bound counted from roundings (u = 2^-24; see _bn_train_ref.check_entry);
   2. the recomputed ReLU decision, bit-identical repeats and graph replays, refusals that launch nothing;
   3. single Units in .train() mode, one per route: autograd graph, tally, forward, gradients, running statistics, caches;
   4. Refinement and SoftAttention.fuse in .train() mode: gradients and buffers against the float64 CPU run, a second
@@ -88,51 +88,9 @@ def _pc(v):
 
 
 def _check_entry(r, shape, first_kind, relu):
-    """The bounds, each from counting roundings with a margin of a small factor:
-      statistics   |mean - mean64| <= 2^-40 mean|z - p|; |var - var64| <= 2^-40 mean (z - p)^2 + 16 x 2^-53 (var64 + eps), var taken
-                   back out of the kernel's invstd as 1 / invstd^2 - eps -- the second term: eight float64 roundings of at
-                   most 2^-53 (var + eps) each (the sum var + eps, the square root and the division in the kernel, the
-                   last two twice in invstd^2; the square, the division and the subtraction here), margin 2; and through
-                   invstd = (var + eps)^-1/2 itself, whose derivative carries
-                   |var - var64| <= 2^-40 mean (z - p)^2 to |invstd - invstd64| <= invstd64 (2^-41 mean (z - p)^2 / (var64 + eps)
-                   + 4 x 2^-53) -- the second term: the square root and the division in float64 -- so that a constant channel
-                   (var = 0 exactly) is held to the roundings of 1 / sqrt(eps) alone;
-      buffers      2 u relative;
-      output       4 u (|xhat64 gamma| + |beta|) + |a| |mean - mean64|;
-      dgamma       4 u sum |gm xhat|, dbeta 2 u sum |gm|, gz 8 u |a| (|gm| + |dbeta| / N + |xhat| |dgamma| / N), the mask [y_gpu > 0]
-                   imposed, every imposed decision that is not float64's own within the output bound of zero."""
+    """The bounds of _bn_train_ref.check_entry, each from counting roundings; and the channel put below zero."""
     d, f = _ref(shape, first_kind, relu)
-    n = shape[0] * shape[2] * shape[3]
-    mean, invstd = r["stats"][0::2], r["stats"][1::2]
-    e_mean = (mean - f["mean"]).abs()
-    assert bool((e_mean <= 2.0 ** -40 * f["dev1"]).all()), ("mean", e_mean, f["dev1"])
-    b_inv = f["invstd"] * (2.0 ** -41 * f["dev2"] / (f["var"] + EPS) + 4 * 2.0 ** -53)
-    assert bool(((invstd - f["invstd"]).abs() <= b_inv).all()), ("invstd", invstd - f["invstd"], b_inv)
-    var = 1.0 / (invstd * invstd) - EPS                       # the kernel's var back out of invstd, in float64
-    b_var = 2.0 ** -40 * f["dev2"] + 16 * 2.0 ** -53 * (f["var"] + EPS)
-    assert bool(((var - f["var"]).abs() <= b_var).all()), ("var", var - f["var"], b_var)
-    for k in ("running_mean", "running_var"):
-        assert bool(((r[k].double() - f[k]).abs() <= 2 * U * f[k].abs()).all()), k
-    a = (d["gamma"].double() * f["invstd"]).abs()
-    b_y = 4 * U * ((f["xhat"] * _pc(d["gamma"].double())).abs() + _pc(d["beta"].double().abs())) + _pc(a * e_mean)
-    e_y = (r["y"].double() - f["y"]).abs()
-    print(shape, first_kind, relu, "y: worst error / bound = %.3g" % float((e_y / b_y.clamp_min(1e-300)).max()))
-    assert bool((e_y <= b_y).all()), "y"
-    mask = None
-    if relu:
-        mask = r["y"] > 0
-        flipped = mask != (f["pre"] > 0)
-        assert bool((f["pre"].abs()[flipped] <= b_y[flipped]).all()), "a ReLU decision far from zero differs from float64's"
-    g = BR.backward(f, d["gy"], d["gamma"], relu, mask)
-    for k, factor in (("dgamma", 4), ("dbeta", 2)):
-        err, bound = (r[k].double() - g[k]).abs(), factor * U * g["abs_" + k]
-        print(shape, first_kind, relu, k, "worst error / bound = %.3g" % float((err / bound.clamp_min(1e-300)).max()))
-        assert bool((err <= bound).all()), (k, err, bound)
-    b_gz = 8 * U * _pc(a) * (g["gm"].abs() + _pc(g["dbeta"].abs()) / n + f["xhat"].abs() * _pc(g["dgamma"].abs()) / n)
-    e_gz = (r["gz"].double() - g["gz"]).abs()
-    print(shape, first_kind, relu, "gz: worst error / bound = %.3g" % float((e_gz / b_gz.clamp_min(1e-300)).max()))
-    assert bool((e_gz <= b_gz).all()), "gz"
-    assert not any(bool(torch.isnan(v).any()) for v in r.values())
+    BR.check_entry(r, f, d["gamma"], d["beta"], d["gy"], relu, EPS, (shape, first_kind, relu))
     if relu and shape[1] > 1:                                   # the channel with every pre-activation below zero
         c = shape[1] - 1
         assert not bool(r["y"][:, c].any()) and not bool(r["gz"][:, c].any())

@@ -3,6 +3,7 @@ tests/_stage0_bn_train_ref.py against torch.nn.BatchNorm3d itself in float64, th
 reference, the new names of the C ABI and of ops2d with the host-side refusals and the workspace query, and the refusals
 of CostRegNetNoDown in .train() mode on CPU tensors."""
 import ctypes
+import glob
 import os
 import re
 
@@ -86,14 +87,13 @@ def test_new_names_in_the_binding_and_in_ops2d():
     src = open(os.path.join(ROOT, "include", "decnet_hip.h")).read()
     assert int(re.search(r"#define\s+DECNET_BN_CL_ROWS\s+(\d+)", src).group(1)) == ops2d.BN_CL_ROWS == SB.ROWS
     assert decnet_amd.BatchNorm3dActFunction is stage0_grad.BatchNorm3dActFunction
-    # one copy of the pre-activation: neither kernel file defines it, both include the shared header
+    # one copy of the pre-activation, in the one kernel file of both layouts, which is built without -fno-honor-nans
     csrc = os.path.join(ROOT, "decnet_amd", "csrc")
-    for f in ("batchnorm.hip", "batchnorm_cl.hip"):
-        txt = open(os.path.join(csrc, f)).read()
-        assert '#include "bn_pre.h"' in txt and not re.search(r"float\s+bn_pre\s*\(", txt), f
-    assert len(re.findall(r"float\s+bn_pre\s*\(", open(os.path.join(csrc, "bn_pre.h")).read())) == 1
+    sources = glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h"))
+    assert sum(len(re.findall(r"float\s+bn_pre\s*\(", open(f).read())) for f in sources) == 1
     from decnet_amd import build
-    assert "batchnorm_cl.hip" not in build.EXTRA_FLAGS                  # built without -fno-honor-nans
+    assert "batchnorm.hip" not in build.EXTRA_FLAGS
+    assert not os.path.exists(os.path.join(csrc, "batchnorm_cl.hip")) and not os.path.exists(os.path.join(csrc, "bn_pre.h"))
 
 
 @pytest.fixture(scope="module")

@@ -1,9 +1,9 @@
-"""Training-mode BatchNorm3d of stage 0 under hip_grad() on the GPU (csrc/batchnorm_cl.hip,
+"""Training-mode BatchNorm3d of stage 0 under hip_grad() on the GPU (csrc/batchnorm.hip, the Columns layout,
 stage0_grad.BatchNorm3dActFunction, CostRegNetNoDown in .train() mode) against the float64 restatements of
 tests/_stage0_bn_train_ref.py:
   1. decnet_bn_train_cl_forward / _backward through the C ABI on channels-last matrices [rows, C] at the edge shapes, at
      both placements and under both LDS poison words (tests/_placement._both), every bound counted from roundings
-     (u = 2^-24; see _check): the bounds of tests/test_bn_train_gpu.py, restated;
+     (u = 2^-24; _bn_train_ref.check_entry): the bounds tests/test_bn_train_gpu.py holds the 2-D entries to;
   2. the recomputed ReLU decision, gz left out, a NaN planted in one channel, a constant channel, bit-identical repeats and
      graph replays, refusals that launch nothing;
   3. BatchNorm3dActFunction behind Conv3dFunction on single units;
@@ -26,7 +26,6 @@ from test_stage0_edges_gpu import TOL_WINO
 
 pytestmark = pytest.mark.gpu
 ERR_NULL, ERR_SHAPE = -1, -2
-U = BR.U32
 EPS, MOM = 1e-5, 0.1
 CASES = SB.entry_cases()
 IDS = ["%dx%d" % c for c in CASES]
@@ -90,56 +89,6 @@ def _ref(rows, C, first_kind, relu):
     return _REFS[key]
 
 
-def _pc(v):
-    return v.view(1, -1, 1, 1)
-
-
-def _check(r, f, gamma, beta, gy, relu, tag, buffers=True):
-    """The bounds of tests/test_bn_train_gpu.py::_check_entry on results in the [1, C, 1, N] view, each from counting
-    roundings with a margin of a small factor (f: the float64 forward of the same z):
-      statistics   |mean - mean64| <= 2^-40 mean|z - p|; |var - var64| <= 2^-40 mean (z - p)^2 + 16 x 2^-53 (var64 + eps), var
-                   taken back out of the kernel's invstd as 1 / invstd^2 - eps (eight float64 roundings of at most
-                   2^-53 (var + eps) each, margin 2); |invstd - invstd64| <= invstd64 (2^-41 mean (z - p)^2 / (var64 + eps)
-                   + 4 x 2^-53), so that a constant channel (var = 0 exactly) is held to the roundings of 1 / sqrt(eps) alone;
-      buffers      2 u relative;
-      output       4 u (|xhat64 gamma| + |beta|) + |a| |mean - mean64|;
-      dgamma       4 u sum |gm xhat|, dbeta 2 u sum |gm|, gz 8 u |a| (|gm| + |dbeta| / N + |xhat| |dgamma| / N), the mask
-                   [y_gpu > 0] imposed, every imposed decision that is not float64's own within the output bound of zero."""
-    n = f["xhat"].shape[-1]
-    mean, invstd = r["stats"][0::2], r["stats"][1::2]
-    e_mean = (mean - f["mean"]).abs()
-    assert bool((e_mean <= 2.0 ** -40 * f["dev1"]).all()), ("mean", e_mean, f["dev1"])
-    b_inv = f["invstd"] * (2.0 ** -41 * f["dev2"] / (f["var"] + EPS) + 4 * 2.0 ** -53)
-    assert bool(((invstd - f["invstd"]).abs() <= b_inv).all()), ("invstd", invstd - f["invstd"], b_inv)
-    var = 1.0 / (invstd * invstd) - EPS                       # the kernel's var back out of invstd, in float64
-    b_var = 2.0 ** -40 * f["dev2"] + 16 * 2.0 ** -53 * (f["var"] + EPS)
-    assert bool(((var - f["var"]).abs() <= b_var).all()), ("var", var - f["var"], b_var)
-    if buffers:
-        for k in ("running_mean", "running_var"):
-            assert bool(((r[k].double() - f[k]).abs() <= 2 * U * f[k].abs()).all()), k
-    g64 = gamma.double()
-    a = (g64 * f["invstd"]).abs()
-    b_y = 4 * U * ((f["xhat"] * _pc(g64)).abs() + _pc(beta.double().abs())) + _pc(a * e_mean)
-    e_y = (r["y"].double() - f["y"]).abs()
-    print(tag, "y: worst error / bound = %.3g" % float((e_y / b_y.clamp_min(1e-300)).max()))
-    assert bool((e_y <= b_y).all()), "y"
-    mask = None
-    if relu:
-        mask = r["y"] > 0
-        flipped = mask != (f["pre"] > 0)
-        assert bool((f["pre"].abs()[flipped] <= b_y[flipped]).all()), "a ReLU decision far from zero differs from float64's"
-    g = BR.backward(f, gy, gamma, relu, mask)
-    for k, factor in (("dgamma", 4), ("dbeta", 2)):
-        err, bound = (r[k].double() - g[k]).abs(), factor * U * g["abs_" + k]
-        print(tag, k, "worst error / bound = %.3g" % float((err / bound.clamp_min(1e-300)).max()))
-        assert bool((err <= bound).all()), (k, err, bound)
-    b_gz = 8 * U * _pc(a) * (g["gm"].abs() + _pc(g["dbeta"].abs()) / n + f["xhat"].abs() * _pc(g["dgamma"].abs()) / n)
-    e_gz = (r["gz"].double() - g["gz"]).abs()
-    print(tag, "gz: worst error / bound = %.3g" % float((e_gz / b_gz.clamp_min(1e-300)).max()))
-    assert bool((e_gz <= b_gz).all()), "gz"
-    assert not any(bool(torch.isnan(v).any()) for v in r.values())
-
-
 @pytest.mark.parametrize("relu", [False, True], ids=["id", "relu"])
 @pytest.mark.parametrize("first_kind", [0, 1, 2], ids=BR.KINDS)
 @pytest.mark.parametrize("case", CASES, ids=IDS)
@@ -147,7 +96,7 @@ def test_entries_against_float64(dev, case, first_kind, relu):
     rows, C = case
     r = _both(_run_entry, rows, C, first_kind, relu)
     d, f = _ref(rows, C, first_kind, relu)
-    _check(r, f, d["gamma"], d["beta"], d["gy"], relu, (case, first_kind, relu))
+    BR.check_entry(r, f, d["gamma"], d["beta"], d["gy"], relu, EPS, (case, first_kind, relu))
     if relu and C > 1:                                          # the channel with every pre-activation below zero
         c = C - 1
         assert not bool(r["y"][:, c].any()) and not bool(r["gz"][:, c].any())
@@ -336,7 +285,7 @@ def test_function_on_units(dev, name):
     stats = torch.stack((f["mean"], f["invstd"]), 1).reshape(-1)          # (the Function keeps its stats: held through y)
     r = {"y": SB.from_cl(y.detach().cpu().reshape(rows, Co)), "stats": stats, "running_mean": rmd.cpu(), "running_var": rvd.cpu(),
          "gz": SB.from_cl(z.grad.cpu().reshape(rows, Co)), "dgamma": gd.grad.cpu(), "dbeta": bd.grad.cpu()}
-    _check(r, f, gamma, beta, SB.from_cl(gy.reshape(rows, Co)), relu, name)
+    BR.check_entry(r, f, gamma, beta, SB.from_cl(gy.reshape(rows, Co)), relu, EPS, name)
 
 
 # ---- 4. the module in .train() mode -------------------------------------------------------------------------------------------

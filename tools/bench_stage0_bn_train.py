@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Timing of stage 0 in .train() mode under decnet_amd.hip_grad() (Conv3dFunction, then BatchNorm3dActFunction over
-csrc/batchnorm_cl.hip) at the stage-0 volumes of config 5 (B = 4, C = 216, 20 x 36, D = 8: 23 040 voxels) and config 2
-(B = 8: 46 080 voxels).
+the Columns layout of csrc/batchnorm.hip) at the stage-0 volumes of config 5 (B = 4, C = 216, 20 x 36, D = 8: 23 040
+voxels) and config 2 (B = 8: 46 080 voxels).
 
     python tools/bench_stage0_bn_train.py [--out profiles/stage0_bn_train.json] [--calls 50] [--repeats 3]
     python tools/bench_stage0_bn_train.py --parity [--out profiles/stage0_bn_train_parity.json]
