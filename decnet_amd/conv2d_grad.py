@@ -29,7 +29,8 @@ with the 1 x 1 convolutions on decnet_conv2d_mfma_cat_bn_act.
 A unit in ``.train()`` mode (``Unit._forward_grad_train``) runs the same conv Function with scale 1, shift 0 and no ReLU,
 then ``BatchNormActFunction``: BatchNorm2d on the statistics of the batch (+ ReLU), forward and backward on
 csrc/batchnorm.hip, the running statistics updated in place by the forward kernel.
-Stage 0 (Conv3d units, BatchNorm3d frozen or on the statistics of the batch) has its own Functions in stage0_grad.py.
+Stage 0 (Conv3d units, BatchNorm3d frozen or on the statistics of the batch) has its own Functions in stage0_grad.py, on
+the parameter side (``_param_grads``) and the identity epilogue (``identity_epilogue``) of this file.
 Out of scope: statistics synchronised across GPUs, ``momentum=None``, the ASPP tap-conv block, the
 20 x 36 stride-1 layers, double backward.
 """
@@ -73,28 +74,28 @@ def flipped_weight(w, scale, rows=None):
     return wt.contiguous()
 
 
-def _param_grads(ctx, gy, wgrad, co_dim=0, first=4):
-    """The parameter side of one unit's backward, shared by every Function here: -> (dw, dscale, dshift, gm, w32, s32).
-    wgrad(xs, gy, y) -> (G, gsum, gm): the weight-gradient entry, launched only when the weight or the scale wants a
-    gradient; co_dim: the output-channel axis of the weight (1 for a transposed layer); first: the position of w among the
-    Function's arguments (scale and shift follow it)."""
+def _param_grads(ctx, gy, wgrad, co_dim=0, first=4, gm_co=1):
+    """The parameter side of one unit's backward, shared by every Function here and by stage0_grad.Conv3dFunction: ->
+    (dw, dscale, dshift, gm, w32, s32).  wgrad(xs, gy, y) -> (G, gsum, gm): the weight-gradient entry, launched only when
+    the weight or the scale wants a gradient; co_dim: the output-channel axis of the weight (1 for a transposed layer),
+    whose rank is the weight's own (4, or 5 for a Conv3d); first: the position of w among the Function's arguments (scale
+    and shift follow it); gm_co: the channel axis of gm (1: NCHW planes, -1: channels-last volumes)."""
     w, scale, y = ctx.saved_tensors[:3]
     need_w, need_scale, need_shift = ctx.needs_input_grad[first:first + 3]
     w32, s32 = w.detach().float().contiguous(), scale.detach().float()
-    sv = s32.view((-1, 1, 1, 1) if co_dim == 0 else (1, -1, 1, 1))
     dw = dscale = dshift = None
     if need_w or need_scale:
         G, gsum, gm = wgrad(ctx.saved_tensors[3:], gy, y)
         if need_w:
-            dw = G * sv
+            dw = G * s32.view([-1 if d == co_dim else 1 for d in range(w.dim())])
         if need_scale:
-            dscale = (w32.double() * G.double()).sum((1, 2, 3) if co_dim == 0 else (0, 2, 3)).float()
+            dscale = (w32.double() * G.double()).sum([d for d in range(w.dim()) if d != co_dim]).float()
         if need_shift:
             dshift = gsum
     else:                                   # no weight gradient wanted: the mask and the sum alone
         gm = gy if y is None else torch.ops.aten.threshold_backward(gy, y, 0)
         if need_shift:
-            dshift = gm.sum((0, 2, 3), dtype=torch.float64).float()
+            dshift = gm.sum([d for d in range(gm.dim()) if d != gm_co % gm.dim()], dtype=torch.float64).float()
     return dw, dscale, dshift, gm, w32, s32
 
 
@@ -124,16 +125,20 @@ def _save(ctx, k, dil, relu, w, scale, y, xs, first=4):
     ctx.save_for_backward(w, scale, y if relu else None, *(xs if need_g else ()))
 
 
+def identity_epilogue(n, device):
+    """(scale, shift) = (ones, zeros) [n]: a forward entry as the plain convolution gm -> dx."""
+    return torch.ones(n, device=device), torch.zeros(n, device=device)
+
+
 def _dx_small(gm, wt, k, dil):
     n, co = wt.shape[0], wt.shape[1]
-    return ops2d.conv2d_bn_act(gm, ops2d.conv2d_pack_weight(wt, False), torch.ones(n, device=gm.device),
-                               torch.zeros(n, device=gm.device), co, k, dil, 0)
+    return ops2d.conv2d_bn_act(gm, ops2d.conv2d_pack_weight(wt, False), *identity_epilogue(n, gm.device), co, k, dil, 0)
 
 
 def _dx_mfma(gm, wt, k, dil):
     n, co = wt.shape[0], wt.shape[1]
-    return ops2d.conv2d_mfma_cat_bn_act([gm], ops2d.conv2d_mfma_pack_weight(wt, co, k), torch.ones(n, device=gm.device),
-                                        torch.zeros(n, device=gm.device), co, k, dil, 0)
+    return ops2d.conv2d_mfma_cat_bn_act([gm], ops2d.conv2d_mfma_pack_weight(wt, co, k), *identity_epilogue(n, gm.device),
+                                        co, k, dil, 0)
 
 
 class Conv2dSmallFunction(Function):
@@ -181,7 +186,7 @@ def _conv1x1_mfma(x, wt):
     """conv1x1(x, wt) for wt [n, C] on the matrix-core forward entry (scale 1, shift 0, no ReLU), packed per backward."""
     n, c = wt.shape
     return ops2d.conv2d_mfma_cat_bn_act([x], ops2d.conv2d_mfma_pack_weight(wt.contiguous(), c, 1),
-                                        torch.ones(n, device=x.device), torch.zeros(n, device=x.device), c, 1, 1, 0)
+                                        *identity_epilogue(n, x.device), c, 1, 1, 0)
 
 
 class Conv2dS3Function(Function):

@@ -17,7 +17,7 @@
 // A layout cuts a channel's values into work items and says which thread walks which elements; an item's elements are
 // p[offset(k)], k = k0, k0 + STEP, ... < n, taken in rising order and accumulated in float64 from the first one on.
 //
-//   Planes    the idiom of loss.hip and conv2d_wgrad_reduce.h: a plane (b, c) is H W consecutive floats, cut into
+//   Planes    the idiom of loss.hip and wgrad_common.h: a plane (b, c) is H W consecutive floats, cut into
 //             segments of DECNET_BN_SEGMENT floats.  A wave owns a segment, lane l takes l, l + 64, ..., the 64 lane sums are added in a
 //             fixed butterfly and lane 0 writes the partial, part [C][B nseg][2].  One finish workgroup per channel
 //             (thread t: t, t + 256, ...; then a fixed tree).

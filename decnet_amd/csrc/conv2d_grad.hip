@@ -14,26 +14,18 @@
 //     straddles x = 0 patches up to three dwords), one batch of four loads per thread;
 //   * the wave reads its operands as 16-byte LDS words (pitch 260: conflict-free) and runs the MFMAs.
 // Partition and order are functions of the shape alone: workgroup v = (b, row block, column block), set 4 v + wave.
-// Each set is written to the caller's workspace [set][Cout][Cin k k + 1]; a second launch adds the sets in float64 --
-// thread (element, s) the sets s, s + 16, ... in rising order, then the 16 sums in rising s -- and rounds once to fp32.
-// No atomics.  The longest fp32 addition chain is one accumulator's MFMA K chain: 64 pixels x RB rows = 512 terms.
-#include "common.h"
-#include "conv2d_wgrad_reduce.h"
+// Each set is written to the caller's workspace [set][Cout][Cin k k + 1]; the second launch is the float64 reduction of
+// csrc/wgrad_common.h, which also states the sequence every weight-gradient entry follows (no mask launch here: gm is
+// formed above).  The longest fp32 addition chain is one accumulator's MFMA K chain: 64 pixels x RB rows = 512 terms.
+#include "wgrad_common.h"
 
 typedef int i32x4_g __attribute__((ext_vector_type(4)));
-typedef float f32x4_g __attribute__((ext_vector_type(4)));
 
 namespace {
 
-constexpr int MAXSEG = 6;
 constexpr int PX = 256;              // columns of a workgroup (64 per wave)
 constexpr int PITCH = PX + 4;        // floats: rows 16-byte aligned, 16 rows x 4 quads hit 64 different banks
 constexpr int RB = 8;                // rows of a workgroup
-struct Segs {
-    const float *p[MAXSEG];
-    int c[MAXSEG];
-    int n;
-};
 
 template <int MT, int NT>
 __global__ __launch_bounds__(256) void conv2d_wgrad_partial(Segs in, const float *__restrict__ gy,
@@ -50,18 +42,18 @@ __global__ __launch_bounds__(256) void conv2d_wgrad_partial(Segs in, const float
     const int kk = k * k, N = cin * kk, h = k / 2;                      // GEMM column N: the ones of gsum
     const size_t plane = (size_t)H * W;
     const bool vec = (W & 3) == 0 && ((uintptr_t)gm & 15) == 0;
-    f32x4_g acc[MT][NT];
+    f32x4 acc[MT][NT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-        for (int j = 0; j < NT; ++j) acc[mt][j] = f32x4_g{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < NT; ++j) acc[mt][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int r = 0; r < rows; ++r) {
         const int yy = y0 + r;
-        f32x4_g a4[MT][4];
+        f32x4 a4[MT][4];
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
             // ---- stage tile j of the taps: wave w the GEMM columns 16 j + 4 w + i, lane q the quad q ----
-            f32x4_g t[4];
+            f32x4 t[4];
             int xs[4];
             __amdgpu_buffer_rsrc_t rr[4];
 #pragma unroll
@@ -78,12 +70,12 @@ __global__ __launch_bounds__(256) void conv2d_wgrad_partial(Segs in, const float
                 rr[i] = __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, ok ? W * 4 : 0, 0x00020000);
                 xs[i] = xq + (reach ? (kx - h) * dil : 0);               // < 0: a huge unsigned offset, reads zeros
                 const i32x4_g u = __builtin_amdgcn_raw_buffer_load_b128(rr[i], (int)((unsigned)xs[i] * 4u), 0, 0);
-                t[i] = f32x4_g{__int_as_float(u.x), __int_as_float(u.y), __int_as_float(u.z), __int_as_float(u.w)};
+                t[i] = f32x4{__int_as_float(u.x), __int_as_float(u.y), __int_as_float(u.z), __int_as_float(u.w)};
             }
             // ---- at the first tile of a row: gm of this row, wave w the channels w, w + 4, ... ----
-            f32x4_g g[MT * 4];
+            f32x4 g[MT * 4];
             if (j == 0) {
-                f32x4_g yv[MT * 4];
+                f32x4 yv[MT * 4];
 #pragma unroll
                 for (int i = 0; i < MT * 4; ++i) {
                     const int co = wave + 4 * i;
@@ -92,13 +84,13 @@ __global__ __launch_bounds__(256) void conv2d_wgrad_partial(Segs in, const float
                     const __amdgpu_buffer_rsrc_t rg =
                         __builtin_amdgcn_make_buffer_rsrc((void *)(gy + off), 0, ok ? W * 4 : 0, 0x00020000);
                     const i32x4_g u = __builtin_amdgcn_raw_buffer_load_b128(rg, xq * 4, 0, 0);
-                    g[i] = f32x4_g{__int_as_float(u.x), __int_as_float(u.y), __int_as_float(u.z), __int_as_float(u.w)};
-                    yv[i] = f32x4_g{1.f, 1.f, 1.f, 1.f};
+                    g[i] = f32x4{__int_as_float(u.x), __int_as_float(u.y), __int_as_float(u.z), __int_as_float(u.w)};
+                    yv[i] = f32x4{1.f, 1.f, 1.f, 1.f};
                     if (yo) {
                         const __amdgpu_buffer_rsrc_t ry =
                             __builtin_amdgcn_make_buffer_rsrc((void *)(yo + off), 0, ok ? W * 4 : 0, 0x00020000);
                         const i32x4_g uy = __builtin_amdgcn_raw_buffer_load_b128(ry, xq * 4, 0, 0);
-                        yv[i] = f32x4_g{__int_as_float(uy.x), __int_as_float(uy.y), __int_as_float(uy.z), __int_as_float(uy.w)};
+                        yv[i] = f32x4{__int_as_float(uy.x), __int_as_float(uy.y), __int_as_float(uy.z), __int_as_float(uy.w)};
                     }
                 }
 #pragma unroll
@@ -106,11 +98,11 @@ __global__ __launch_bounds__(256) void conv2d_wgrad_partial(Segs in, const float
                     const int co = wave + 4 * i;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) g[i][e] = yv[i][e] > 0.f ? g[i][e] : 0.f;
-                    *reinterpret_cast<f32x4_g *>(&At[co * PITCH + 4 * lane]) = g[i];
+                    *reinterpret_cast<f32x4 *>(&At[co * PITCH + 4 * lane]) = g[i];
                     if (gm && co < Cout) {
                         float *gp = gm + ((size_t)b * Cout + co) * plane + (size_t)yy * W + xq;
                         if (vec) {
-                            if (xq < W) *reinterpret_cast<f32x4_g *>(gp) = g[i];
+                            if (xq < W) *reinterpret_cast<f32x4 *>(gp) = g[i];
                         } else {
 #pragma unroll
                             for (int e = 0; e < 4; ++e)
@@ -128,8 +120,8 @@ __global__ __launch_bounds__(256) void conv2d_wgrad_partial(Segs in, const float
                         if (xs[i] + e >= 0)
                             t[i][e] = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(rr[i], (xs[i] + e) * 4, 0, 0));
                 }
-                if (n == N) t[i] = f32x4_g{1.f, 1.f, 1.f, 1.f};
-                *reinterpret_cast<f32x4_g *>(&Bt[(4 * wave + i) * PITCH + 4 * lane]) = t[i];
+                if (n == N) t[i] = f32x4{1.f, 1.f, 1.f, 1.f};
+                *reinterpret_cast<f32x4 *>(&Bt[(4 * wave + i) * PITCH + 4 * lane]) = t[i];
             }
             __syncthreads();
             // ---- the wave's 64 columns: four groups of 16 pixels, lane (m, kq) the pixels 16 g + 4 kq + e ----
@@ -139,11 +131,11 @@ __global__ __launch_bounds__(256) void conv2d_wgrad_partial(Segs in, const float
                 for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
                     for (int gq = 0; gq < 4; ++gq)
-                        a4[mt][gq] = *reinterpret_cast<const f32x4_g *>(&At[(mt * 16 + m) * PITCH + px + 16 * gq]);
+                        a4[mt][gq] = *reinterpret_cast<const f32x4 *>(&At[(mt * 16 + m) * PITCH + px + 16 * gq]);
             }
 #pragma unroll
             for (int gq = 0; gq < 4; ++gq) {
-                const f32x4_g b4 = *reinterpret_cast<const f32x4_g *>(&Bt[m * PITCH + px + 16 * gq]);
+                const f32x4 b4 = *reinterpret_cast<const f32x4 *>(&Bt[m * PITCH + px + 16 * gq]);
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
 #pragma unroll
@@ -191,25 +183,14 @@ size_t decnet_conv2d_wgrad_workspace_floats(int B, int Cin, int Cout, int H, int
 int decnet_conv2d_wgrad(const float *const *xs, const int *cins, int nseg, const float *gy, const float *y, float *gm,
                         float *G, float *gsum, float *workspace, size_t workspace_floats, int B, int Cout, int H,
                         int W, int k, int dilation, void *stream) {
-    if (!xs || !cins || !gy || !G || !gsum || !workspace || (y && !gm)) return DECNET_ERR_NULL_POINTER;
-    if (nseg < 1 || nseg > MAXSEG) return DECNET_ERR_UNSUPPORTED;
-    if (B < 1 || Cout < 1 || H < 1 || W < 1 || dilation < 1) return DECNET_ERR_BAD_SHAPE;
     Segs in{};
-    int cin = 0;
-    for (int i = 0; i < nseg; ++i) {
-        if (!xs[i]) return DECNET_ERR_NULL_POINTER;
-        if (cins[i] < 1) return DECNET_ERR_BAD_SHAPE;
-        if (cins[i] > 24) return DECNET_ERR_UNSUPPORTED;
-        in.p[i] = xs[i]; in.c[i] = cins[i];
-        cin += cins[i];
-    }
-    in.n = nseg;
-    if ((k != 1 && k != 3) || Cout > 24 || cin > 24) return DECNET_ERR_UNSUPPORTED;
-    if ((double)B * (cin > Cout ? cin : Cout) * H * W >= 9.0e18) return DECNET_ERR_BAD_SHAPE;
+    int cin, rc;
+    if ((rc = wgrad_stride1_args(xs, cins, nseg, gy, y, gm, G, gsum, workspace, B, Cout, H, W, k, dilation, 24, &in, &cin)))
+        return rc;
     const long T = wgrad_groups(B, cin, Cout, H, W, k);
     if (T == 0) return DECNET_ERR_UNSUPPORTED;
-    if (workspace_floats < decnet_conv2d_wgrad_workspace_floats(B, cin, Cout, H, W, k)) return DECNET_ERR_BAD_SHAPE;
-    if ((uintptr_t)workspace & 15) return DECNET_ERR_MISALIGNED;
+    if ((rc = wgrad_workspace(workspace, workspace_floats, decnet_conv2d_wgrad_workspace_floats(B, cin, Cout, H, W, k))))
+        return rc;
     hipStream_t s = (hipStream_t)stream;
     const int N1 = cin * k * k + 1, tiles = ceil_div(N1, 16), gx = ceil_div(W, PX), nrb = ceil_div(H, RB);
     const dim3 grid((unsigned)T);
@@ -224,11 +205,8 @@ int decnet_conv2d_wgrad(const float *const *xs, const int *cins, int nseg, const
     if (Cout <= 16) GON(1); else GON(2);
 #undef GON
 #undef GO
-    int rc = decnet_launch_status();
-    if (rc) return rc;
-    hipLaunchKernelGGL(conv2d_wgrad_reduce, dim3((unsigned)ceil_div(Cout * N1, 16)), dim3(256), 0, s, workspace, G, gsum,
-                       (int)(T * 4), Cout, N1);
-    return decnet_launch_status();
+    if ((rc = decnet_launch_status())) return rc;
+    return launch_wgrad_reduce(workspace, G, gsum, T * 4, Cout, N1, s);
 }
 
 }  // extern "C"

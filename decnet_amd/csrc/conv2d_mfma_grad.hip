@@ -5,8 +5,7 @@
 //     gsum[co]          = sum_{b,y,x} gm[b][co][y][x]
 // for Cout, Cin <= 224, where G (up to 224 x 2017 with the column of ones that yields gsum) no longer fits one wave.
 //
-// Three launches, all on the caller's stream:
-//   1. conv2d_relu_mask forms gm once (skipped when gm is NULL: no ReLU, gm is gy);
+// The sequence is that of csrc/wgrad_common.h (mask, GEMM into partial sets, float64 reduction); this file holds its step
 //   2. conv2d_mfma_wgrad_partial runs the GEMM [Cout x pixels] . [pixels x (Cin k k + 1)] on v_mfma_f32_16x16x4_f32 (bit
 //      for bit an fp32 fma chain over the pixels).  A 256-thread workgroup owns every row of G (MT tiles of 16 channels),
 //      one block of 64 NT GEMM columns (wave w the tiles w NT .. w NT + NT - 1: 4 MT NT accumulator registers) and one
@@ -16,7 +15,6 @@
 //      unconditionally from an address clamped into the plane and selected afterwards, at any float alignment.  The loads
 //      of chunk c + 1 are in flight while the MFMAs of chunk c run.  The tap rows' plane pointers and offsets sit in the
 //      registers of the wave's lanes and are handed out by v_readlane.
-//   3. conv2d_wgrad_reduce (csrc/conv2d_wgrad_reduce.h) adds the partial sets in a fixed order in float64 and rounds once.
 // LDS: (16 MT + 64 NT) rows x 272 bytes; NT = 2 up to MT = 6 (60 928 bytes), NT = 1 above (MT = 14: 78 336 bytes), so two
 // workgroups fit the 160 KiB of a CU; __launch_bounds__(256, 2) keeps the registers to that too.
 // Partition and order are functions of the shape alone (plan() below): workgroup v = (b, slice, column block), set
@@ -40,28 +38,14 @@
 // without gm: NULL_POINTER; a dimension < 1, fewer workspace floats than the query: BAD_SHAPE (the planes of gy, y and gm
 // follow from H and W); Cin or Cout > 224, B or the coarse H > 65535, a fine plane >= 2^29 floats: UNSUPPORTED; a workspace
 // off 16 bytes: MISALIGNED.
-#include "common.h"
-#include "conv2d_wgrad_reduce.h"
-
-typedef float f32x4_w __attribute__((ext_vector_type(4)));
+#include "wgrad_common.h"
 
 namespace {
 
-constexpr int MAXSEG = 6;
 constexpr int MAXCH = 224;           // Cout and Cin
 constexpr int CP = 64;               // pixels of a chunk: 64 consecutive pixels of the plane, one per lane
 constexpr int PITCH = CP + 4;        // floats: rows 16-byte aligned, 16 rows x 4 quads hit 64 different banks
 constexpr int MAXSL = 64, MINSL = 8; // chunks of a slice: the fp32 chain is 64 sl terms
-struct Segs {
-    const float *p[MAXSEG];
-    int c[MAXSEG];
-    int n;
-};
-__global__ __launch_bounds__(256) void conv2d_relu_mask(const float *__restrict__ gy, const float *__restrict__ y,
-                                                        float *__restrict__ gm, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
-        gm[i] = !y || y[i] > 0.f ? gy[i] : 0.f;
-}
 
 // the float i of the global array at address `base`: a wave-uniform base and a 32-bit byte offset per lane (a plane is
 // below 2^29 floats)
@@ -150,11 +134,11 @@ __global__ __launch_bounds__(256, 2) void conv2d_mfma_wgrad_partial(Segs in, con
             okb |= ok << i;
         }
     };
-    f32x4_w acc[MT][NT];
+    f32x4 acc[MT][NT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-        for (int j = 0; j < NT; ++j) acc[mt][j] = f32x4_w{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < NT; ++j) acc[mt][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     load(c0);
     for (int c = c0; c < c1; ++c) {
 #pragma unroll
@@ -170,16 +154,16 @@ __global__ __launch_bounds__(256, 2) void conv2d_mfma_wgrad_partial(Segs in, con
 #pragma unroll
         for (int gq = 0; gq < 4; ++gq) {
             const int px = 16 * gq + 4 * kq;
-            f32x4_w b4[NT];
+            f32x4 b4[NT];
 #pragma unroll
             for (int j = 0; j < NT; ++j)
-                b4[j] = *reinterpret_cast<const f32x4_w *>(&Bt[((wave * NT + j) * 16 + m) * PITCH + px]);
+                b4[j] = *reinterpret_cast<const f32x4 *>(&Bt[((wave * NT + j) * 16 + m) * PITCH + px]);
 #pragma unroll
             for (int m0 = 0; m0 < MT; m0 += MG) {                       // (MG row tiles at a time: their operands in registers)
-                f32x4_w a4[MG];
+                f32x4 a4[MG];
 #pragma unroll
                 for (int mt = 0; mt < MG; ++mt)
-                    if (m0 + mt < MT) a4[mt] = *reinterpret_cast<const f32x4_w *>(&At[((m0 + mt) * 16 + m) * PITCH + px]);
+                    if (m0 + mt < MT) a4[mt] = *reinterpret_cast<const f32x4 *>(&At[((m0 + mt) * 16 + m) * PITCH + px]);
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
 #pragma unroll
@@ -322,16 +306,11 @@ int s3_wgrad(bool tr, const float *x, const float *gy, const float *y, float *gm
     if (Cin > MAXCH || Cout > MAXCH) return DECNET_ERR_UNSUPPORTED;
     const PlanS3 q = plan_s3(tr, B, Cin, Cout, H, W);
     if (q.floats == 0) return DECNET_ERR_UNSUPPORTED;
-    if (workspace_floats < q.floats) return DECNET_ERR_BAD_SHAPE;
-    if ((uintptr_t)workspace & 15) return DECNET_ERR_MISALIGNED;
+    int rc;
+    if ((rc = wgrad_workspace(workspace, workspace_floats, q.floats))) return rc;
     hipStream_t s = (hipStream_t)stream;
     const size_t gplane = tr ? (size_t)q.hf * q.wf : (size_t)q.hc * q.wc;       // of gy, y, gm
-    int rc;
-    if (gm) {
-        const size_t n = (size_t)B * Cout * gplane, blocks = (n + 1023) / 1024;
-        hipLaunchKernelGGL(conv2d_relu_mask, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, s, gy, y, gm, n);
-        if ((rc = decnet_launch_status())) return rc;
-    }
+    if ((rc = launch_relu_mask(gy, y, gm, (size_t)B * Cout * gplane, s))) return rc;
     const float *g = y ? gm : gy;
     Segs in{};
     in.p[0] = tr ? g : x; in.c[0] = q.cq; in.n = 1;
@@ -339,9 +318,7 @@ int s3_wgrad(bool tr, const float *x, const float *gy, const float *y, float *gm
         return rc;
     const int N1 = q.cq * 9 + 1;
     float *ones = tr ? workspace + q.sets_floats : gsum;                        // the sums of P
-    hipLaunchKernelGGL(conv2d_wgrad_reduce, dim3((unsigned)ceil_div(q.cp * N1, 16)), dim3(256), 0, s, workspace, G, ones,
-                       (int)q.p.sets, q.cp, N1);
-    if ((rc = decnet_launch_status()) || !tr) return rc;
+    if ((rc = launch_wgrad_reduce(workspace, G, ones, q.p.sets, q.cp, N1, s)) || !tr) return rc;
     double *part = reinterpret_cast<double *>(workspace + q.sets_floats + (((size_t)Cin + 3) & ~(size_t)3));
     hipLaunchKernelGGL(chan_sum_partial, dim3((unsigned)q.nsum, (unsigned)Cout, (unsigned)B), dim3(256), 0, s, g, part, Cout,
                        gplane, (int)q.nsum);
@@ -384,38 +361,18 @@ size_t decnet_conv2d_mfma_wgrad_workspace_floats(int B, int Cin, int Cout, int H
 int decnet_conv2d_mfma_wgrad(const float *const *xs, const int *cins, int nseg, const float *gy, const float *y, float *gm,
                              float *G, float *gsum, float *workspace, size_t workspace_floats, int B, int Cout, int H,
                              int W, int k, int dilation, void *stream) {
-    if (!xs || !cins || !gy || !G || !gsum || !workspace || (y && !gm)) return DECNET_ERR_NULL_POINTER;
-    if (nseg < 1 || nseg > MAXSEG) return DECNET_ERR_UNSUPPORTED;
-    if (B < 1 || Cout < 1 || H < 1 || W < 1 || dilation < 1) return DECNET_ERR_BAD_SHAPE;
     Segs in{};
-    int cin = 0;
-    for (int i = 0; i < nseg; ++i) {
-        if (!xs[i]) return DECNET_ERR_NULL_POINTER;
-        if (cins[i] < 1) return DECNET_ERR_BAD_SHAPE;
-        if (cins[i] > MAXCH) return DECNET_ERR_UNSUPPORTED;
-        in.p[i] = xs[i]; in.c[i] = cins[i];
-        cin += cins[i];
-    }
-    in.n = nseg;
-    if ((k != 1 && k != 3) || Cout > MAXCH || cin > MAXCH) return DECNET_ERR_UNSUPPORTED;
-    if ((double)B * (cin > Cout ? cin : Cout) * H * W >= 9.0e18) return DECNET_ERR_BAD_SHAPE;
+    int cin, rc;
+    if ((rc = wgrad_stride1_args(xs, cins, nseg, gy, y, gm, G, gsum, workspace, B, Cout, H, W, k, dilation, MAXCH, &in, &cin)))
+        return rc;
     const Plan p = plan(B, cin, Cout, H, W, k);
     if (p.sets == 0) return DECNET_ERR_UNSUPPORTED;
-    if (workspace_floats < decnet_conv2d_mfma_wgrad_workspace_floats(B, cin, Cout, H, W, k)) return DECNET_ERR_BAD_SHAPE;
-    if ((uintptr_t)workspace & 15) return DECNET_ERR_MISALIGNED;
+    if ((rc = wgrad_workspace(workspace, workspace_floats, decnet_conv2d_mfma_wgrad_workspace_floats(B, cin, Cout, H, W, k))))
+        return rc;
     hipStream_t s = (hipStream_t)stream;
-    int rc;
-    if (gm) {                                                         // (without y: a copy, as decnet_conv2d_wgrad)
-        const size_t n = (size_t)B * Cout * H * W, blocks = (n + 1023) / 1024;
-        hipLaunchKernelGGL(conv2d_relu_mask, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, s, gy, y, gm, n);
-        if ((rc = decnet_launch_status())) return rc;
-    }
-    const float *a = y ? gm : gy;
-    if ((rc = launch_partial<false>(p, in, a, workspace, Cout, cin, H, W, k, dilation, 0, 0, s))) return rc;
-    const int N1 = cin * k * k + 1;
-    hipLaunchKernelGGL(conv2d_wgrad_reduce, dim3((unsigned)ceil_div(Cout * N1, 16)), dim3(256), 0, s, workspace, G, gsum,
-                       (int)p.sets, Cout, N1);
-    return decnet_launch_status();
+    if ((rc = launch_relu_mask(gy, y, gm, (size_t)B * Cout * H * W, s))) return rc;   // (without y: a copy, as decnet_conv2d_wgrad)
+    if ((rc = launch_partial<false>(p, in, y ? gm : gy, workspace, Cout, cin, H, W, k, dilation, 0, 0, s))) return rc;
+    return launch_wgrad_reduce(workspace, G, gsum, p.sets, Cout, cin * k * k + 1, s);
 }
 
 }  // extern "C"

@@ -6,8 +6,8 @@
 //     gsum[co]              = sum_{b,d,h,w} gm[b,d,h,w,co]
 // G in torch's [Co,Ci,3,3,3] layout, so that dW = scale G, dscale = <w, G>, dshift = gsum.
 //
-// Three launches, all on the caller's stream:
-//   1. conv3d_relu_mask forms gm once (skipped when gm is NULL: no ReLU, gm is gy);
+// The sequence is that of csrc/wgrad_common.h (mask, GEMM into partial sets, float64 reduction, here with TAPS = 27: it
+// writes the torch layout); this file holds its step
 //   2. conv3d_wgrad_partial runs the GEMM [Co x voxels] . [voxels x (27 Ci + 1)] on v_mfma_f32_16x16x4_f32 (bit for bit an
 //      fp32 fma chain over the voxels).  GEMM column n = tap Ci + ci, tap = 9 kd + 3 kh + kw; column 27 Ci is the column
 //      of ones that yields gsum.  Both operands are channels-last, so a chunk of KC = 32 consecutive voxels of gm is ONE
@@ -20,9 +20,6 @@
 //      of a wave (lane (m, kq): voxel 4 ks + kq, channel / column m) hit 64 different banks.  Which of the 27 taps of a
 //      voxel meet the volume is one 27-bit word per voxel, formed a chunk ahead by the first 32 threads.  Every LDS word
 //      that is read is written first: rows co >= Co and the voxels past the end of the slice hold zeros.
-//   3. conv3d_wgrad_reduce adds the partial sets in a fixed order in float64 -- thread (element, s) the sets s, s + 16, ...
-//      in rising order, then the 16 sums in rising s, as csrc/conv2d_wgrad_reduce.h -- rounds once and writes the torch
-//      layout.
 // Partition and order are functions of the shape alone (plan() below): set s holds the voxels [s sl, min((s + 1) sl, V)) of
 // the V = B D H W, with sl a power of two: 4096, halved down to 256 while the launch has fewer than 1024 workgroups.  The
 // workspace is [set][Co][27 Ci + 1].  No atomics.  The longest fp32 addition chain is one accumulator's MFMA K chain over
@@ -30,7 +27,7 @@
 // Limits: Ci a multiple of 4 (as the forward entries), Ci, Co <= 224, V max(Ci, Co) < 2^31 (element offsets are 32-bit).
 // Refusals (nothing launched): NULL, also y without gm: NULL_POINTER; a dimension < 1, fewer workspace floats than the
 // query: BAD_SHAPE; Ci % 4, Ci or Co > 224, the size limit: UNSUPPORTED; a workspace off 16 bytes: MISALIGNED.
-#include "common.h"
+#include "wgrad_common.h"
 
 namespace {
 
@@ -41,12 +38,6 @@ constexpr int BP = NB + 16;           // floats; 16 mod 64: the 4 voxels x 16 co
 constexpr int MAXSL = 4096, MINSL = 256;   // voxels of a slice: the fp32 chain is sl terms
 
 constexpr int a_pitch(int mt) { return (mt * 16 + 47) / 64 * 64 + 16; }      // >= 16 mt, 16 mod 64
-
-__global__ __launch_bounds__(256) void conv3d_relu_mask(const float *__restrict__ gy, const float *__restrict__ y,
-                                                        float *__restrict__ gm, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
-        gm[i] = !y || y[i] > 0.f ? gy[i] : 0.f;
-}
 
 template <int MT>
 __global__ __launch_bounds__(256, 2) void conv3d_wgrad_partial(const float *__restrict__ x, const float *__restrict__ gm,
@@ -91,10 +82,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_wgrad_partial(const float *__re
     for (int i = t; i < KC * AP; i += 256) At[i] = 0.f;                 // (the rows co >= Co stay zero)
     mask_of(vbeg, 0);
     __syncthreads();
-    typedef float f32x4_g __attribute__((ext_vector_type(4)));
-    f32x4_g acc[MT];
+    f32x4 acc[MT];
 #pragma unroll
-    for (int mt = 0; mt < MT; ++mt) acc[mt] = f32x4_g{0.f, 0.f, 0.f, 0.f};
+    for (int mt = 0; mt < MT; ++mt) acc[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int qa = 256 / Co, ra = 256 - qa * Co;                        // thread t walks the chunk's gm in steps of 256 floats
     constexpr int NA = 2 * MT;                                          // KC * 16 MT / 256: its steps at most
     // The loads of the chunk at v0, all issued before the first is used: the chunk's gm is the KC Co floats from gm + v0 Co
@@ -166,31 +156,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_wgrad_partial(const float *__re
         }
 }
 
-// G[co][ci][tap] (GEMM column tap Ci + ci) and gsum[co] (column 27 Ci) = the float64 sum of the `nsets` partial sets,
-// rounded once; the order of conv2d_wgrad_reduce.
-__global__ __launch_bounds__(256) void conv3d_wgrad_reduce(const float *__restrict__ ws, float *__restrict__ G,
-                                                           float *__restrict__ gsum, int nsets, int Co, int Ci) {
-    __shared__ double part[16][17];
-    const int e = threadIdx.x & 15, s = threadIdx.x >> 4;
-    const int N1 = 27 * Ci + 1;
-    const long total = (long)Co * N1, el = (long)blockIdx.x * 16 + e;
-    double a = 0.0;
-    if (el < total)
-        for (int set = s; set < nsets; set += 16) a += (double)ws[(size_t)set * total + el];
-    part[s][e] = a;
-    __syncthreads();
-    if (s == 0 && el < total) {
-        double r = 0.0;
-        for (int i = 0; i < 16; ++i) r += part[i][e];
-        const int co = (int)(el / N1), n = (int)(el - (long)co * N1);
-        if (n == N1 - 1) gsum[co] = (float)r;
-        else {
-            const int tap = n / Ci, ci = n - tap * Ci;
-            G[((size_t)co * Ci + ci) * 27 + tap] = (float)r;
-        }
-    }
-}
-
 // the partition of a shape (nsets == 0: not covered)
 struct Plan {
     int mt, ncb, sl, V;
@@ -229,15 +194,10 @@ int decnet_conv3d_wgrad(const float *x, const float *gy, const float *y, float *
     if (B < 1 || D < 1 || H < 1 || W < 1 || Ci < 1 || Co < 1) return DECNET_ERR_BAD_SHAPE;
     const Plan p = plan(B, D, H, W, Ci, Co);
     if (p.nsets == 0) return DECNET_ERR_UNSUPPORTED;
-    if (workspace_floats < decnet_conv3d_wgrad_workspace_floats(B, D, H, W, Ci, Co)) return DECNET_ERR_BAD_SHAPE;
-    if ((uintptr_t)workspace & 15) return DECNET_ERR_MISALIGNED;
-    hipStream_t s = (hipStream_t)stream;
     int rc;
-    if (gm) {                                                         // (without y: a copy, as decnet_conv2d_mfma_wgrad)
-        const size_t n = (size_t)p.V * Co, blocks = (n + 1023) / 1024;
-        hipLaunchKernelGGL(conv3d_relu_mask, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, s, gy, y, gm, n);
-        if ((rc = decnet_launch_status())) return rc;
-    }
+    if ((rc = wgrad_workspace(workspace, workspace_floats, decnet_conv3d_wgrad_workspace_floats(B, D, H, W, Ci, Co)))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = launch_relu_mask(gy, y, gm, (size_t)p.V * Co, s))) return rc;   // (without y: a copy, as decnet_conv2d_mfma_wgrad)
     const float *a = y ? gm : gy;
     const dim3 grid((unsigned)(p.nsets * p.ncb));
 #define GO(MT_)                                                                                                       \
@@ -252,10 +212,7 @@ int decnet_conv3d_wgrad(const float *x, const float *gy, const float *y, float *
     }
 #undef GO
     if ((rc = decnet_launch_status())) return rc;
-    const long total = (long)Co * (27 * Ci + 1);
-    hipLaunchKernelGGL(conv3d_wgrad_reduce, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, s, workspace, G, gsum,
-                       (int)p.nsets, Co, Ci);
-    return decnet_launch_status();
+    return launch_wgrad_reduce<27>(workspace, G, gsum, p.nsets, Co, 27 * Ci + 1, s);
 }
 
 }  // extern "C"

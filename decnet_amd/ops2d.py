@@ -115,12 +115,37 @@ def conv2d_cat_epilogue(xs, w, scale, shift, cin, k, dil, relu, epi, ea, eb=None
     return _conv2d_cat("decnet_conv2d_cat_epilogue", _F32, xs, w, scale, shift, cin, k, dil, relu, out, int(epi), ea, eb)
 
 
-_WGRAD_FLOATS = {}
+_WORKSPACE_FLOATS = {}
+
+
+def _workspace_floats(name, dims, what):
+    """The floats of workspace that entry decnet_`name` takes at `dims`: the library's size query, cached per entry and
+    shape.  0 -- a shape the entry does not cover -- raises; what: the format of dims in that message."""
+    n = _WORKSPACE_FLOATS.get((name,) + dims)
+    if n is None:
+        n = _WORKSPACE_FLOATS[(name,) + dims] = int(size(name + "_workspace_floats", *dims))
+    if n == 0:
+        raise _lib.DecnetHipError(("decnet_%s does not cover " + what) % ((name,) + dims))
+    return n
+
+
+def _wgrad_call(name, lead, gy, y, Co, G_shape, dims, what, tail):
+    """The common end of the weight-gradient wrappers: decnet_`name`(lead..., gy, y, gm, G, gsum, workspace, its floats,
+    tail...) -> (G, gsum, gm; gy itself without y).  The workspace comes from torch.empty, its size from
+    _workspace_floats(name, dims, what)."""
+    nws = _workspace_floats(name, dims, what)
+    dev = gy.device
+    G = torch.empty(G_shape, dtype=_F32, device=dev)
+    gsum = torch.empty((Co,), dtype=_F32, device=dev)
+    gm = gy if y is None else torch.empty_like(gy)
+    ws = torch.empty(nws, dtype=_F32, device=dev)                      # torch allocations are 16-byte aligned
+    _call("decnet_" + name, gy, *lead, gy.data_ptr(), None if y is None else y.data_ptr(),
+          None if y is None else gm.data_ptr(), G.data_ptr(), gsum.data_ptr(), ws.data_ptr(), nws, *tail)
+    return G, gsum, gm
 
 
 def _wgrad(name, xs, gy, y, k, dil):
-    """One weight-gradient entry `name` (decnet_conv2d_wgrad / decnet_conv2d_mfma_wgrad: one argument list).  The
-    workspace comes from torch.empty, its size from the library's query, cached per entry and shape."""
+    """One stride-1 weight-gradient entry `name` (conv2d_wgrad / conv2d_mfma_wgrad: one argument list)."""
     B, Co, H, W = _chk("gy", gy).shape
     if y is not None:
         _chk("y", y, (B, Co, H, W))
@@ -128,21 +153,9 @@ def _wgrad(name, xs, gy, y, k, dil):
         _chk("input part", t, (B, t.shape[1], H, W))
     cins, n = [int(t.shape[1]) for t in xs], len(xs)
     cin, k, dil = sum(cins), int(k), int(dil)
-    key = (B, cin, Co, H, W, k)
-    nws = _WGRAD_FLOATS.get((name,) + key)
-    if nws is None:
-        nws = _WGRAD_FLOATS[(name,) + key] = int(size(name + "_workspace_floats", *key))
-    if nws == 0:
-        raise _lib.DecnetHipError("decnet_%s does not cover B %d, Cin %d, Cout %d, %d x %d, k %d" % ((name,) + key))
-    dev = gy.device
-    G = torch.empty((Co, cin, k, k), dtype=_F32, device=dev)
-    gsum = torch.empty((Co,), dtype=_F32, device=dev)
-    gm = gy if y is None else torch.empty_like(gy)
-    ws = torch.empty(nws, dtype=_F32, device=dev)                      # torch allocations are 16-byte aligned
-    _call("decnet_" + name, gy, (ctypes.c_void_p * n)(*[t.data_ptr() for t in xs]), (ctypes.c_int * n)(*cins), n,
-          gy.data_ptr(), None if y is None else y.data_ptr(), None if y is None else gm.data_ptr(), G.data_ptr(),
-          gsum.data_ptr(), ws.data_ptr(), nws, B, Co, H, W, k, dil)
-    return G, gsum, gm
+    lead = ((ctypes.c_void_p * n)(*[t.data_ptr() for t in xs]), (ctypes.c_int * n)(*cins), n)
+    return _wgrad_call(name, lead, gy, y, Co, (Co, cin, k, k), (B, cin, Co, H, W, k),
+                       "B %d, Cin %d, Cout %d, %d x %d, k %d", (B, Co, H, W, k, dil))
 
 
 def conv2d_wgrad(xs, gy, y, k, dil):
@@ -165,20 +178,9 @@ def _wgrad_s3(name, tr, x, gy, y):
     _chk("gy", gy, (B, Co, 3 * H, 3 * W) if tr else (B, Co, (H - 1) // 3 + 1, (W - 1) // 3 + 1))
     if y is not None:
         _chk("y", y, gy.shape)
-    key = (name, B, Ci, Co, H, W)
-    nws = _WGRAD_FLOATS.get(key)
-    if nws is None:
-        nws = _WGRAD_FLOATS[key] = int(size(name + "_workspace_floats", *key[1:]))
-    if nws == 0:
-        raise _lib.DecnetHipError("decnet_%s does not cover B %d, Cin %d, Cout %d, %d x %d" % key)
-    dev = gy.device
-    G = torch.empty((Ci, Co, 3, 3) if tr else (Co, Ci, 3, 3), dtype=_F32, device=dev)
-    gsum = torch.empty((Co,), dtype=_F32, device=dev)
-    gm = gy if y is None else torch.empty_like(gy)
-    ws = torch.empty(nws, dtype=_F32, device=dev)                      # torch allocations are 16-byte aligned
-    _call("decnet_" + name, gy, x.data_ptr(), gy.data_ptr(), None if y is None else y.data_ptr(),
-          None if y is None else gm.data_ptr(), G.data_ptr(), gsum.data_ptr(), ws.data_ptr(), nws, B, Ci, Co, H, W)
-    return G, gsum, gm
+    dims = (B, Ci, Co, H, W)
+    return _wgrad_call(name, (x.data_ptr(),), gy, y, Co, (Ci, Co, 3, 3) if tr else (Co, Ci, 3, 3), dims,
+                       "B %d, Cin %d, Cout %d, %d x %d", dims)
 
 
 def conv2d_k3s3_wgrad(x, gy, y):
@@ -355,9 +357,6 @@ def warp_disparity_backward(right, disp, gout, want_right=True, want_disp=True):
     return gr, gd
 
 
-_UPS_BWD_FLOATS = {}
-
-
 def dynamic_upsample3_backward(logits, disp, gout, want_disp=True):
     """-> (g_logits [B,81,h,w], g_disp [B,h,w] or None).  The workspace comes from torch.empty, its size from the library's
     query, cached per shape."""
@@ -368,11 +367,7 @@ def dynamic_upsample3_backward(logits, disp, gout, want_disp=True):
     gd = ws = None
     nws = 0
     if want_disp:
-        nws = _UPS_BWD_FLOATS.get((B, h, w))
-        if nws is None:
-            nws = _UPS_BWD_FLOATS[(B, h, w)] = int(size("dynamic_upsample3_backward_workspace_floats", B, h, w))
-        if nws == 0:
-            raise _lib.DecnetHipError("decnet_dynamic_upsample3_backward does not cover B %d, %d x %d" % (B, h, w))
+        nws = _workspace_floats("dynamic_upsample3_backward", (B, h, w), "B %d, %d x %d")
         gd = torch.empty_like(disp)
         ws = torch.empty(nws, dtype=_F32, device=disp.device)         # torch allocations are 16-byte aligned
     _call("decnet_dynamic_upsample3_backward", logits, logits.data_ptr(), disp.data_ptr(), gout.data_ptr(), gl.data_ptr(),
@@ -487,20 +482,9 @@ def conv3d_wgrad(x, gy, y, dims, Ci, Co):
     _chk("gy", gy, dims + (Co,))
     if y is not None:
         _chk("y", y, dims + (Co,))
-    key = ("conv3d_wgrad",) + dims + (int(Ci), int(Co))
-    nws = _WGRAD_FLOATS.get(key)
-    if nws is None:
-        nws = _WGRAD_FLOATS[key] = int(size("conv3d_wgrad_workspace_floats", *key[1:]))
-    if nws == 0:
-        raise _lib.DecnetHipError("decnet_%s does not cover B %d, D %d, %d x %d, Ci %d, Co %d" % key)
-    dev = gy.device
-    G = torch.empty((Co, Ci, 3, 3, 3), dtype=_F32, device=dev)
-    gsum = torch.empty((Co,), dtype=_F32, device=dev)
-    gm = gy if y is None else torch.empty_like(gy)
-    ws = torch.empty(nws, dtype=_F32, device=dev)                      # torch allocations are 16-byte aligned
-    _call("decnet_conv3d_wgrad", gy, x.data_ptr(), gy.data_ptr(), None if y is None else y.data_ptr(),
-          None if y is None else gm.data_ptr(), G.data_ptr(), gsum.data_ptr(), ws.data_ptr(), nws, *dims, Ci, Co)
-    return G, gsum, gm
+    dims += (int(Ci), int(Co))
+    return _wgrad_call("conv3d_wgrad", (x.data_ptr(),), gy, y, Co, (Co, Ci, 3, 3, 3), dims,
+                       "B %d, D %d, %d x %d, Ci %d, Co %d", dims)
 
 
 def conv3d_wino_stack_bn_act(x, layers, res_src, res_dst, out, ws, dims, C, variant):

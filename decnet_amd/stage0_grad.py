@@ -7,7 +7,7 @@ ReLU):
 
     G[co,ci,kd,kh,kw] = sum gm[b,d,h,w,co] * x[b,d+kd-1,h+kh-1,w+kw-1,ci]       decnet_conv3d_wgrad (csrc/conv3d_grad.hip)
     gsum[co]          = sum gm[b,d,h,w,co]
-    dW = scale[co] * G[co],  dscale[co] = <w[co], G[co]>,  dshift = gsum         (torch)
+    dW = scale[co] * G[co],  dscale[co] = <w[co], G[co]>,  dshift = gsum         (torch: conv2d_grad._param_grads)
     dx = conv(gm, W'),  W'[ci][co][kd][kh][kw] = w[co][ci][2-kd][2-kh][2-kw] * scale[co]: the forward entry, packed per
          backward (nothing is cached: the weights change every step)
 
@@ -31,7 +31,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import ops2d
-from .conv2d_grad import bn_act_backward, bn_act_forward
+from .conv2d_grad import _param_grads, bn_act_backward, bn_act_forward, identity_epilogue
 
 
 def flipped_weight3d(w, scale):
@@ -114,25 +114,11 @@ class Conv3dFunction(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        w, scale, y, x = ctx.saved_tensors
-        need_w, need_scale, need_shift, need_x = ctx.needs_input_grad[2:6]
-        gy = gy.contiguous()
-        w32, s32 = w.detach().float().contiguous(), scale.detach().float()
         dims, Ci, Co = ctx.dims, ctx.ci, ctx.co
-        dw = dscale = dshift = dx = None
-        if need_w or need_scale:
-            G, gsum, gm = ops2d.conv3d_wgrad(x, gy, y, dims, Ci, Co)
-            if need_w:
-                dw = G * s32.view(-1, 1, 1, 1, 1)
-            if need_scale:
-                dscale = (w32.double() * G.double()).sum((1, 2, 3, 4)).float()
-            if need_shift:
-                dshift = gsum
-        else:                                   # no weight gradient wanted: the mask and the sum alone
-            gm = gy if y is None else torch.ops.aten.threshold_backward(gy, y, 0)
-            if need_shift:
-                dshift = gm.sum((0, 1, 2, 3), dtype=torch.float64).float()
-        if need_x:                              # the forward entry on gm: Co -> Ci channels, scale 1, shift 0, no ReLU
+        dw, dscale, dshift, gm, w32, s32 = _param_grads(
+            ctx, gy.contiguous(), lambda xs, g, y: ops2d.conv3d_wgrad(xs[0], g, y, dims, Ci, Co), first=2, gm_co=-1)
+        dx = None
+        if ctx.needs_input_grad[5]:             # the forward entry on gm: Co -> Ci channels, scale 1, shift 0, no ReLU
             wt, cin = flipped_weight3d(w32, s32), Co
             if Co % 4:                          # (the last unit: one channel) the entries take channels in fours
                 pad = 4 - Co % 4
@@ -140,8 +126,7 @@ class Conv3dFunction(Function):
                 wt = torch.nn.functional.pad(wt, (0, 0, 0, 0, 0, 0, 0, pad))
                 cin = Co + pad
             ops = unit_operands(wt, ctx.variant)
-            dx = _run_entry(ops, gm, torch.ones(Ci, device=gm.device), torch.zeros(Ci, device=gm.device), dims, cin, Ci,
-                            False, ctx.ws)
+            dx = _run_entry(ops, gm, *identity_epilogue(Ci, gm.device), dims, cin, Ci, False, ctx.ws)
         return (None, None, dw, dscale, dshift, dx)
 
 
