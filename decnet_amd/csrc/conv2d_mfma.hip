@@ -21,23 +21,9 @@
 // bf16] (one ds_read_b128 per lane = one A operand, conflict free); the weights are split at packing time and
 // streamed from L2 as ready-made B operands (one 16-byte load per lane), each used for TM MFMAs.
 // Epilogue: relu(acc * scale + shift) -> NCHW, 64-byte runs per (channel, row).
-#include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
+#include "conv2d_mfma_common.h"
 
 namespace {
-
-constexpr int MAXSEG = 6;
-constexpr int THREADS = 256;
-
-struct Segs {
-    const float *p[MAXSEG];
-    int c[MAXSEG];
-    int n;
-};
 
 // output-channel tiles (of 16) per workgroup, and the padded tile count of a layer
 __host__ __device__ inline int pick_tn(int Cout) {
@@ -47,38 +33,6 @@ __host__ __device__ inline int pick_tn(int Cout) {
 __host__ __device__ inline int padded_nt(int Cout) {
     const int tn = pick_tn(Cout), nt = (Cout + 15) >> 4;
     return (nt + tn - 1) / tn * tn;
-}
-
-__device__ __forceinline__ void split3(float x, int &h, int &m, int &l) {
-    // round-to-nearest-even terms (v_cvt_pk_bf16_f32): |x - h| <= 2^-9 |x|, |x - h - m| <= 2^-18 |x|, and the residual
-    // that l leaves is <= 2^-27 |x| -- truncated terms (round 2) left 2^-24 and, worse, always of the sign of x, so the
-    // dropped m.l / l.m products of a K-long sum added up instead of averaging out (tests/test_inputdata_gpu.py measures
-    // the network's distance to its float64 run: 1.35 x the reference's float32 distance before, 1.0 x after)
-    h = __float_as_int((float)(__bf16)x);
-    const float r1 = x - __int_as_float(h);
-    m = __float_as_int((float)(__bf16)r1);
-    l = __float_as_int((float)(__bf16)(r1 - __int_as_float(m)));
-}
-
-// eight values -> the three packed operand registers sets {hi, mid, lo}[4] (pairs (x[2e], x[2e+1]) share a register):
-// the same terms as split3, two per v_cvt_pk_bf16_f32 -- the packed pair IS the operand register, and a term's float
-// value is a shift / a mask of it (no v_perm_b32, half the conversions, packed subtractions)
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ int pack_bf16(float a, float b) {
-    return __builtin_bit_cast(int, __builtin_convertvector(f32x2{a, b}, bf16x2));
-}
-__device__ __forceinline__ void split3x8(const float (&x)[8], i32x4 &th, i32x4 &tm, i32x4 &tl) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const float x0 = x[2 * e], x1 = x[2 * e + 1];
-        const int h = pack_bf16(x0, x1);
-        const float r0 = x0 - __int_as_float(h << 16), r1 = x1 - __int_as_float(h & 0xffff0000);
-        const int m = pack_bf16(r0, r1);
-        th[e] = h;
-        tm[e] = m;
-        tl[e] = pack_bf16(r0 - __int_as_float(m << 16), r1 - __int_as_float(m & 0xffff0000));
-    }
 }
 
 // w [Cout][Cin][KT] -> wp[chunk][tap][j][n tile][lane] (16 bytes: the lane's 8 bf16 of the B operand)
@@ -109,63 +63,6 @@ __global__ void conv2d_mfma_pack(const float *__restrict__ w, i32x4 *__restrict_
 #pragma unroll
     for (int e = 0; e < 4; ++e) o[e] = __builtin_amdgcn_perm(t[2 * e + 1], t[2 * e], 0x07060302);
     wp[idx] = o;
-}
-
-// Epilogue of both kernels: the lane holds output channel n = tile * 16 + r of the pixels x0 + 4 q .. + 3 of TM rows.
-// shuf = 0: y [B,Cout,H,W] = act(acc * scale[n] + shift[n]).  shuf = C (transposed convolution k = 3, stride 3, as a
-// 1 x 1 convolution to 9 C channels n = 9 co + 3 ky + kx): y [B,C,3H,3W] at (3 row + ky, 3 x + kx), scale / shift per co.
-template <int TM, int TN>
-__device__ __forceinline__ void conv2d_mfma_store(const f32x4 (&acc)[TM][TN], const float *__restrict__ scale,
-                                                  const float *__restrict__ shift, float *__restrict__ y, int b, int Cout,
-                                                  int H, int W, int relu, int nt0, int r, int q, int x0, int row0,
-                                                  int shuf) {
-    const size_t HW = (size_t)H * W;
-    const int xq = x0 + 4 * q;
-    const bool vec = (W & 3) == 0 && ((uintptr_t)y & 15) == 0 && xq + 3 < W;   // y: any dense fp32 pointer
-#pragma unroll
-    for (int nt = 0; nt < TN; ++nt) {
-        const int n = (nt0 + nt) * 16 + r;
-        if (n >= Cout) continue;
-        if (shuf) {
-            const int co = n / 9, kk = n - 9 * co, ky = kk / 3, kx = kk - 3 * ky;
-            const float sc = scale[co], sh = shift[co];
-            float *yp = y + ((size_t)b * shuf + co) * 9 * HW;
-#pragma unroll
-            for (int mt = 0; mt < TM; ++mt) {
-                const int row = row0 + mt;
-                if (row >= H) break;
-                float *dst = yp + ((size_t)(3 * row + ky) * 3 * W) + kx;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    float v = fmaf(acc[mt][nt][i], sc, sh);
-                    if (relu) v = fmaxf(v, 0.f);
-                    if (xq + i < W) dst[3 * (xq + i)] = v;
-                }
-            }
-            continue;
-        }
-        const float sc = scale[n], sh = shift[n];
-        float *yp = y + ((size_t)b * Cout + n) * HW;
-#pragma unroll
-        for (int mt = 0; mt < TM; ++mt) {
-            const int row = row0 + mt;
-            if (row >= H) break;
-            f32x4 v = acc[mt][nt];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                v[i] = fmaf(v[i], sc, sh);
-                if (relu) v[i] = fmaxf(v[i], 0.f);
-            }
-            float *dst = yp + (size_t)row * W + xq;
-            if (vec) {
-                *reinterpret_cast<f32x4 *>(dst) = v;
-            } else {
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    if (xq + i < W) dst[i] = v[i];
-            }
-        }
-    }
 }
 
 // NU: staging units per thread, 128 NU >= pixels of the halo tile
@@ -490,36 +387,15 @@ template <int TM, int TN, int NU, bool PC>
 int launch(const Segs &in, const i32x4 *wp, const float *scale, const float *shift, float *y, int B, int Cout, int H,
            int W, int KT, int dil, int relu, int nchunk, int NT, int shuf, hipStream_t stream) {
     const int pad = KT == 9 ? dil : 0;
-    const size_t lds = (size_t)(16 + 2 * pad) * (4 * TM + 2 * pad) * 6 * 16 * (PC ? 2 : 1);
+    const size_t lds = (size_t)tile_pixels(TM, pad) * 6 * 16 * (PC ? 2 : 1);
     if (lds > DECNET_LDS_BYTES) return DECNET_ERR_UNSUPPORTED;
-    int cin = 0;
-    for (int i = 0; i < in.n; ++i) cin += in.c[i];
-    const int tail8 = cin - 16 * (nchunk - 1) <= 8;              // the last chunk's channels 8-15 are padding
-    const int tiles_x = ceil_div(W, 16), tiles_y = ceil_div(H, 4 * TM);
-    const dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)(NT / TN), (unsigned)B);
-    // more than 64 KiB of dynamic LDS needs the attribute; set per launch (it is per device, and cheap)
-    if constexpr (PC) {
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void *)conv2d_mfma_pc<TM, TN, NU>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return (int)e;
-        }
-        hipLaunchKernelGGL((conv2d_mfma_pc<TM, TN, NU>), grid, dim3(2 * THREADS), lds, stream, in, wp, scale, shift, y,
-                           Cout, H, W, KT, dil, relu, nchunk, NT, tiles_x, tail8, shuf);
-    } else {
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void *)conv2d_mfma<TM, TN, NU>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return (int)e;
-        }
-        hipLaunchKernelGGL((conv2d_mfma<TM, TN, NU>), grid, dim3(THREADS), lds, stream, in, wp, scale, shift, y, Cout, H,
-                           W, KT, dil, relu, nchunk, NT, tiles_x, tail8, shuf);
-    }
-    return decnet_launch_status();
+    if constexpr (PC)
+        return conv2d_mfma_launch(conv2d_mfma_pc<TM, TN, NU>, 2 * THREADS, lds, TM, NT / TN, in, wp, scale, shift, y, B,
+                                  Cout, H, W, KT, dil, relu, nchunk, NT, shuf, stream);
+    else
+        return conv2d_mfma_launch(conv2d_mfma<TM, TN, NU>, THREADS, lds, TM, NT / TN, in, wp, scale, shift, y, B, Cout, H,
+                                  W, KT, dil, relu, nchunk, NT, shuf, stream);
 }
-
-// pixels of the halo tile of a TM variant
-inline int tile_pixels(int tm, int pad) { return (16 + 2 * pad) * (4 * tm + 2 * pad); }
 
 template <int TN, bool PC>
 int launch_tm(int tm, const Segs &in, const i32x4 *wp, const float *scale, const float *shift, float *y, int B,
@@ -546,63 +422,20 @@ int launch_tm(int tm, const Segs &in, const i32x4 *wp, const float *scale, const
 
 }  // namespace
 
-// ---- DECNET_CONV2D_ACC=2: every entry point below forwards to conv2d_mfma_acc2.hip (two accumulator sets) ----------
-extern "C" {
-size_t decnet_conv2d_mfma_packed_bytes_acc2(int Cin, int Cout, int k);
-int decnet_conv2d_mfma_pack_weight_acc2(const float *w, void *w_packed, int Cin, int Cout, int k, void *stream);
-size_t decnet_deconv2d_mfma_packed_bytes_acc2(int Cin, int Cout);
-int decnet_deconv2d_mfma_pack_weight_acc2(const float *w, void *w_packed, int Cin, int Cout, void *stream);
-int decnet_conv2d_mfma_cat_bn_act_acc2(const float *const *xs, const int *cins, int nseg, const void *w_packed,
-                                       const float *scale, const float *shift, float *y, int B, int Cout, int H, int W,
-                                       int k, int dilation, int relu, void *stream);
-int decnet_deconv2d_mfma_k3s3_bn_act_acc2(const float *x, const void *w_packed, const float *scale, const float *shift,
-                                          float *y, int B, int Cin, int Cout, int H, int W, int relu, void *stream);
-}
-static bool acc2_mode() {
+static bool acc2_mode() {                                     // DECNET_CONV2D_ACC=2: conv2d_mfma_acc2.hip (two accumulator sets)
     static const bool on = [] { const char *e = getenv("DECNET_CONV2D_ACC"); return e && atoi(e) == 2; }();
     return on;
 }
 
-extern "C" {
-
-size_t decnet_conv2d_mfma_packed_bytes(int Cin, int Cout, int k) {
-    if (acc2_mode()) return decnet_conv2d_mfma_packed_bytes_acc2(Cin, Cout, k);
+static size_t packed_bytes(int Cin, int Cout, int k) {
     if (Cin < 1 || Cout < 1 || (k != 1 && k != 3)) return 0;
     const size_t blocks = (size_t)ceil_div(Cin, 16) * (k * k) * 3 + 3;       // + 3: the prefetch runs three blocks ahead
     return blocks * padded_nt(Cout) * 64 * 16;
 }
 
 static int pack_impl(const float *w, void *w_packed, int Cin, int Cout, int k, int tr, void *stream) {
-    if (!w || !w_packed) return DECNET_ERR_NULL_POINTER;
-    const size_t bytes = decnet_conv2d_mfma_packed_bytes(Cin, Cout, k);
-    if (!bytes) return DECNET_ERR_UNSUPPORTED;
-    const int NT = padded_nt(Cout);
-    const long total = (long)ceil_div(Cin, 16) * (k * k) * 3 * NT * 64;
-    hipError_t e = hipMemsetAsync((char *)w_packed + (size_t)total * 16, 0, bytes - (size_t)total * 16,
-                                  (hipStream_t)stream);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(conv2d_mfma_pack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w,
-                       (i32x4 *)w_packed, Cin, Cout, k * k, NT, total, tr);
-    return decnet_launch_status();
-}
-
-int decnet_conv2d_mfma_pack_weight(const float *w, void *w_packed, int Cin, int Cout, int k, void *stream) {
-    if ((uintptr_t)w_packed & 15) return DECNET_ERR_MISALIGNED;       // read / written in 16-byte units
-    if (acc2_mode()) return decnet_conv2d_mfma_pack_weight_acc2(w, w_packed, Cin, Cout, k, stream);
-    return pack_impl(w, w_packed, Cin, Cout, k, 0, stream);
-}
-
-size_t decnet_deconv2d_mfma_packed_bytes(int Cin, int Cout) {
-    if (acc2_mode()) return decnet_deconv2d_mfma_packed_bytes_acc2(Cin, Cout);
-    if (Cout < 1 || Cout > 7281) return 0;
-    return decnet_conv2d_mfma_packed_bytes(Cin, 9 * Cout, 1);
-}
-
-int decnet_deconv2d_mfma_pack_weight(const float *w, void *w_packed, int Cin, int Cout, void *stream) {
-    if ((uintptr_t)w_packed & 15) return DECNET_ERR_MISALIGNED;       // read / written in 16-byte units
-    if (acc2_mode()) return decnet_deconv2d_mfma_pack_weight_acc2(w, w_packed, Cin, Cout, stream);
-    if (Cout < 1 || Cout > 7281) return DECNET_ERR_UNSUPPORTED;
-    return pack_impl(w, w_packed, Cin, 9 * Cout, 1, 1, stream);
+    return conv2d_mfma_pack_launch(conv2d_mfma_pack, w, w_packed, packed_bytes(Cin, Cout, k), Cin, Cout, k * k,
+                                   padded_nt(Cout), 3, tr, stream);
 }
 
 static int run_impl(const Segs &in, long Cin, const void *w_packed, const float *scale, const float *shift, float *y,
@@ -634,42 +467,47 @@ static int run_impl(const Segs &in, long Cin, const void *w_packed, const float 
     return DECNET_ERR_UNSUPPORTED;
 }
 
+extern "C" {
+
+size_t decnet_conv2d_mfma_packed_bytes(int Cin, int Cout, int k) {
+    return acc2_mode() ? conv2d_mfma_packed_bytes_acc2(Cin, Cout, k) : packed_bytes(Cin, Cout, k);
+}
+
+int decnet_conv2d_mfma_pack_weight(const float *w, void *w_packed, int Cin, int Cout, int k, void *stream) {
+    if ((uintptr_t)w_packed & 15) return DECNET_ERR_MISALIGNED;       // read / written in 16-byte units
+    return (acc2_mode() ? conv2d_mfma_pack_acc2 : pack_impl)(w, w_packed, Cin, Cout, k, 0, stream);
+}
+
+size_t decnet_deconv2d_mfma_packed_bytes(int Cin, int Cout) {
+    if (Cout < 1 || Cout > 7281) return 0;
+    return decnet_conv2d_mfma_packed_bytes(Cin, 9 * Cout, 1);
+}
+
+int decnet_deconv2d_mfma_pack_weight(const float *w, void *w_packed, int Cin, int Cout, void *stream) {
+    if ((uintptr_t)w_packed & 15) return DECNET_ERR_MISALIGNED;       // read / written in 16-byte units
+    if (Cout < 1 || Cout > 7281) return DECNET_ERR_UNSUPPORTED;
+    return (acc2_mode() ? conv2d_mfma_pack_acc2 : pack_impl)(w, w_packed, Cin, 9 * Cout, 1, 1, stream);
+}
+
 int decnet_conv2d_mfma_cat_bn_act(const float *const *xs, const int *cins, int nseg, const void *w_packed,
                                   const float *scale, const float *shift, float *y, int B, int Cout, int H, int W,
                                   int k, int dilation, int relu, void *stream) {
     if ((uintptr_t)w_packed & 15) return DECNET_ERR_MISALIGNED;       // read / written in 16-byte units
-    if (acc2_mode())
-        return decnet_conv2d_mfma_cat_bn_act_acc2(xs, cins, nseg, w_packed, scale, shift, y, B, Cout, H, W, k, dilation, relu,
-                                                  stream);
-    if (!xs || !cins || !w_packed || !scale || !shift || !y) return DECNET_ERR_NULL_POINTER;
-    if (nseg < 1 || nseg > MAXSEG || (k != 1 && k != 3)) return DECNET_ERR_UNSUPPORTED;
-    if (B < 1 || Cout < 1 || H < 1 || W < 1 || dilation < 1) return DECNET_ERR_BAD_SHAPE;
-    Segs in{};
-    long Cin = 0;
-    for (int i = 0; i < nseg; ++i) {
-        if (!xs[i]) return DECNET_ERR_NULL_POINTER;
-        if (cins[i] < 1) return DECNET_ERR_BAD_SHAPE;
-        in.p[i] = xs[i];
-        in.c[i] = cins[i];
-        Cin += cins[i];
-    }
-    in.n = nseg;
-    return run_impl(in, Cin, w_packed, scale, shift, y, B, Cout, H, W, k, dilation, relu, 0, stream);
+    Segs in;
+    long Cin;
+    if (int rc = conv2d_mfma_cat_args(xs, cins, nseg, w_packed, scale, shift, y, B, Cout, H, W, k, dilation, &in, &Cin))
+        return rc;
+    return (acc2_mode() ? conv2d_mfma_run_acc2 : run_impl)(in, Cin, w_packed, scale, shift, y, B, Cout, H, W, k, dilation,
+                                                           relu, 0, stream);
 }
 
 int decnet_deconv2d_mfma_k3s3_bn_act(const float *x, const void *w_packed, const float *scale, const float *shift,
                                      float *y, int B, int Cin, int Cout, int H, int W, int relu, void *stream) {
     if ((uintptr_t)w_packed & 15) return DECNET_ERR_MISALIGNED;       // read / written in 16-byte units
-    if (acc2_mode())
-        return decnet_deconv2d_mfma_k3s3_bn_act_acc2(x, w_packed, scale, shift, y, B, Cin, Cout, H, W, relu, stream);
-    if (!x || !w_packed || !scale || !shift || !y) return DECNET_ERR_NULL_POINTER;
-    if (B < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1) return DECNET_ERR_BAD_SHAPE;
-    if (Cout > 7281) return DECNET_ERR_UNSUPPORTED;
-    Segs in{};
-    in.p[0] = x;
-    in.c[0] = Cin;
-    in.n = 1;
-    return run_impl(in, Cin, w_packed, scale, shift, y, B, 9 * Cout, H, W, 1, 1, relu, Cout, stream);
+    Segs in;
+    if (int rc = conv2d_mfma_deconv_args(x, w_packed, scale, shift, y, B, Cin, Cout, H, W, &in)) return rc;
+    return (acc2_mode() ? conv2d_mfma_run_acc2 : run_impl)(in, Cin, w_packed, scale, shift, y, B, 9 * Cout, H, W, 1, 1, relu,
+                                                           Cout, stream);
 }
 
 }  // extern "C"

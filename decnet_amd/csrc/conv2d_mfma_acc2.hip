@@ -1,27 +1,16 @@
 // decnet_amd/csrc/conv2d_mfma_acc2.hip -- conv2d_mfma.hip with TWO accumulator sets: the accuracy option of the bf16x3
-// 2-D trunk (DECNET_CONV2D_ACC=2, read once per process by conv2d_mfma.hip, which forwards its entry points to the
-// *_acc2 functions here; the packed weight format differs, so the switch covers packing and launching alike).
+// 2-D trunk (DECNET_CONV2D_ACC=2, read once per process by conv2d_mfma.hip, whose entry points make their refusals and
+// call the three functions at the end of this file; the packed weight format differs, so the switch covers packing and
+// launching alike).
 // Round 4 measured it (tools/experiments then): error against float64 0.58 x the one-accumulator kernel's, i.e. below an
 // fp32 fma chain's, for 20 - 50 % of the layer time.  Round 5 ships it as the supported way to reference-grade fp32 in the
 // many-channel layers (the alternative was DECNET_CONV2D_MFMA=0: the library's kernels).
-// decnet_amd/csrc/conv2d_mfma.hip -- the many-channel Conv2dUnit layers of the 2-D trunk on the matrix cores.
 //
-// Replaces (eval mode) the library convolution behind
-//   * FeatureExtraction conv1.* / conv2.* / conv3_2.* and the Deconv2dBlock convs   submodule.py:245-343, 162-178
-//   * DynamicUpsampling.weight_learning (73/217/649 -> 81 -> 81 -> 81)               submodule.py:566-589
-//   * Refinement convs at 24..72 channels                                            submodule.py:690-717
-// i.e. Conv2d k = 3 (any dilation, padding = dilation) or k = 1, stride 1, followed by the folded BatchNorm and
-// ReLU of Conv2dUnit.forward (submodule.py:15-45), optionally on the channel concatenation of up to six tensors.
-//
-// Arithmetic: implicit GEMM  Y[pixel][co] = sum_tap sum_ci X[pixel + tap][ci] * Wt[tap][ci][co]  on
-// v_mfma_f32_16x16x32_bf16 at fp32 accuracy: every fp32 operand is split into three bf16 terms
-// x = hi + mid + lo (round to nearest with exact residuals, 24 mantissa bits together) and the six products above 2^-24
-// (hh hm mh mm hl lh) go into the K axis of three MFMAs per 16 input channels (8-channel halves 0 / 1, k groups
-// q = lane >> 4):
+// The layers, the implicit GEMM, the three bf16 terms per operand and the LDS tile are those of conv2d_mfma.hip: read its
+// header comment first.  What differs is where the six term products go (8-channel halves 0 / 1, k groups q = lane >> 4):
 //   j = 0 : A {h0 h0 h1 h1} x B {h0 m0 h1 m1}   -> acc   (hh, hm)
 //   j = 1 : A {m0 m0 m1 m1} x the SAME B tile   -> small (mh, mm)
 //   j = 2 : A {h0 l0 h1 l1} x B {l0 h0 l1 h1}   -> small (hl, lh)
-// against 4 x v_mfma_f32_16x16x4_f32 of 32 cycles each for the same 16 channels: 3 x 16 cycles.
 // Two accumulator sets (round 4).  The instruction rounds its fp32 accumulator after each of its four k groups
 // (tools/ubench/bf16x3_grouping.hip: the error of a long sum follows the NUMBER of k groups added into the big accumulator,
 // whatever their size), so all three MFMAs into one accumulator are 12 roundings per 16 channels at the sum's own size
@@ -33,30 +22,13 @@
 // Tiling: a wave owns TM rows x 16 columns of output pixels x TNW x 16 output channels (TM x TNW accumulator tiles, twice);
 // a workgroup is 4 NH waves: 4 row groups x NH channel halves over ONE halo tile of the input (NH = 2: 512 threads for
 // layers of 49 - 96 output channels -- the second accumulator set halves the channel tiles a wave can hold, the second
-// wave group keeps the staging work per output where it was).  Per 16-channel chunk the halo tile is split once into its
-// bf16 terms and kept in LDS as [term][8-channel group][pixel][8 x bf16] (one ds_read_b128 per lane = one A operand; the
-// k groups q = 0 / 1 and 2 / 3 of an operand are served in the same LDS cycles (MI355X_MICROARCH.md, LDS), so they read
-// the same plane or planes 4 apart: 4 P x 16 bytes is a multiple of 256 for every tile shape); the weights are split at
-// packing time and streamed from L2 as ready-made B operands (one 16-byte load per lane), each used for TM (j = 2) or
-// 2 TM (j = 0, 1) MFMAs.
+// wave group keeps the staging work per output where it was).  The k groups q = 0 / 1 and 2 / 3 of an A operand are served
+// in the same LDS cycles (MI355X_MICROARCH.md, LDS), so they read the same plane or planes 4 apart: 4 P x 16 bytes is a
+// multiple of 256 for every tile shape.  A weight tile is used for TM (j = 2) or 2 TM (j = 0, 1) MFMAs.
 // Epilogue: relu((acc + small) * scale + shift) -> NCHW, 64-byte runs per (channel, row).
-#include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
+#include "conv2d_mfma_common.h"
 
 namespace {
-
-constexpr int MAXSEG = 6;
-constexpr int THREADS = 256;
-
-struct Segs {
-    const float *p[MAXSEG];
-    int c[MAXSEG];
-    int n;
-};
 
 // output-channel tiles (of 16) per workgroup (2, 3: one wave group; 4, 6: two wave groups of 2 / 3 tiles), and the padded
 // tile count of a layer
@@ -71,38 +43,6 @@ __host__ __device__ inline int pick_tn(int Cout) {
 __host__ __device__ inline int padded_nt(int Cout) {
     const int tn = pick_tn(Cout), nt = (Cout + 15) >> 4;
     return (nt + tn - 1) / tn * tn;
-}
-
-__device__ __forceinline__ void split3(float x, int &h, int &m, int &l) {
-    // round-to-nearest-even terms (v_cvt_pk_bf16_f32): |x - h| <= 2^-9 |x|, |x - h - m| <= 2^-18 |x|, and the residual
-    // that l leaves is <= 2^-27 |x| -- truncated terms (round 2) left 2^-24 and, worse, always of the sign of x, so the
-    // dropped m.l / l.m products of a K-long sum added up instead of averaging out (tests/test_inputdata_gpu.py measures
-    // the network's distance to its float64 run: 1.35 x the reference's float32 distance before, 1.0 x after)
-    h = __float_as_int((float)(__bf16)x);
-    const float r1 = x - __int_as_float(h);
-    m = __float_as_int((float)(__bf16)r1);
-    l = __float_as_int((float)(__bf16)(r1 - __int_as_float(m)));
-}
-
-// eight values -> the three packed operand registers sets {hi, mid, lo}[4] (pairs (x[2e], x[2e+1]) share a register):
-// the same terms as split3, two per v_cvt_pk_bf16_f32 -- the packed pair IS the operand register, and a term's float
-// value is a shift / a mask of it (no v_perm_b32, half the conversions, packed subtractions)
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ int pack_bf16(float a, float b) {
-    return __builtin_bit_cast(int, __builtin_convertvector(f32x2{a, b}, bf16x2));
-}
-__device__ __forceinline__ void split3x8(const float (&x)[8], i32x4 &th, i32x4 &tm, i32x4 &tl) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const float x0 = x[2 * e], x1 = x[2 * e + 1];
-        const int h = pack_bf16(x0, x1);
-        const float r0 = x0 - __int_as_float(h << 16), r1 = x1 - __int_as_float(h & 0xffff0000);
-        const int m = pack_bf16(r0, r1);
-        th[e] = h;
-        tm[e] = m;
-        tl[e] = pack_bf16(r0 - __int_as_float(m << 16), r1 - __int_as_float(m & 0xffff0000));
-    }
 }
 
 // w [Cout][Cin][KT] -> wp[chunk][tap][X | Y][n tile][lane] (16 bytes: the lane's 8 bf16 of the B operand)
@@ -142,63 +82,6 @@ __global__ void conv2d_mfma_pack(const float *__restrict__ w, i32x4 *__restrict_
 #pragma unroll
     for (int e = 0; e < 4; ++e) o[e] = __builtin_amdgcn_perm(t[2 * e + 1], t[2 * e], 0x07060302);
     wp[idx] = o;
-}
-
-// Epilogue of both kernels: the lane holds output channel n = tile * 16 + r of the pixels x0 + 4 q .. + 3 of TM rows.
-// shuf = 0: y [B,Cout,H,W] = act(acc * scale[n] + shift[n]).  shuf = C (transposed convolution k = 3, stride 3, as a
-// 1 x 1 convolution to 9 C channels n = 9 co + 3 ky + kx): y [B,C,3H,3W] at (3 row + ky, 3 x + kx), scale / shift per co.
-template <int TM, int TN>
-__device__ __forceinline__ void conv2d_mfma_store(const f32x4 (&acc)[TM][TN], const float *__restrict__ scale,
-                                                  const float *__restrict__ shift, float *__restrict__ y, int b, int Cout,
-                                                  int H, int W, int relu, int nt0, int r, int q, int x0, int row0,
-                                                  int shuf) {
-    const size_t HW = (size_t)H * W;
-    const int xq = x0 + 4 * q;
-    const bool vec = (W & 3) == 0 && ((uintptr_t)y & 15) == 0 && xq + 3 < W;   // y: any dense fp32 pointer
-#pragma unroll
-    for (int nt = 0; nt < TN; ++nt) {
-        const int n = (nt0 + nt) * 16 + r;
-        if (n >= Cout) continue;
-        if (shuf) {
-            const int co = n / 9, kk = n - 9 * co, ky = kk / 3, kx = kk - 3 * ky;
-            const float sc = scale[co], sh = shift[co];
-            float *yp = y + ((size_t)b * shuf + co) * 9 * HW;
-#pragma unroll
-            for (int mt = 0; mt < TM; ++mt) {
-                const int row = row0 + mt;
-                if (row >= H) break;
-                float *dst = yp + ((size_t)(3 * row + ky) * 3 * W) + kx;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    float v = fmaf(acc[mt][nt][i], sc, sh);
-                    if (relu) v = fmaxf(v, 0.f);
-                    if (xq + i < W) dst[3 * (xq + i)] = v;
-                }
-            }
-            continue;
-        }
-        const float sc = scale[n], sh = shift[n];
-        float *yp = y + ((size_t)b * Cout + n) * HW;
-#pragma unroll
-        for (int mt = 0; mt < TM; ++mt) {
-            const int row = row0 + mt;
-            if (row >= H) break;
-            f32x4 v = acc[mt][nt];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                v[i] = fmaf(v[i], sc, sh);
-                if (relu) v[i] = fmaxf(v[i], 0.f);
-            }
-            float *dst = yp + (size_t)row * W + xq;
-            if (vec) {
-                *reinterpret_cast<f32x4 *>(dst) = v;
-            } else {
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    if (xq + i < W) dst[i] = v[i];
-            }
-        }
-    }
 }
 
 // ---- the MFMAs of one 16-channel chunk for one wave ---------------------------------------------------------------------
@@ -502,8 +385,7 @@ __global__ __launch_bounds__(THREADS * NH + THREADS, 1) void conv2d_mfma_pc(
     }
 }
 
-// pixels of the halo tile of a TM variant; staging units per thread
-constexpr int tile_pixels(int tm, int pad) { return (16 + 2 * pad) * (4 * tm + 2 * pad); }
+// staging units per thread
 constexpr int staging_units(int tm, int nh, bool pc, bool dilated) {
     return ((dilated ? 640 : tile_pixels(tm, 1)) + (pc ? 128 : 128 * nh) - 1) / (pc ? 128 : 128 * nh);
 }
@@ -538,30 +420,12 @@ int launch(const Segs &in, const i32x4 *wp, const float *scale, const float *shi
     const int pad = KT == 9 ? dil : 0;
     const size_t lds = (size_t)tile_pixels(TM, pad) * 6 * 16 * (PC ? 2 : 1);
     if (lds > DECNET_LDS_BYTES || tile_pixels(TM, pad) > NU * (PC ? 128 : 128 * NH)) return DECNET_ERR_UNSUPPORTED;
-    int cin = 0;
-    for (int i = 0; i < in.n; ++i) cin += in.c[i];
-    const int tail8 = cin - 16 * (nchunk - 1) <= 8;              // the last chunk's channels 8-15 are padding
-    const int tiles_x = ceil_div(W, 16), tiles_y = ceil_div(H, 4 * TM);
-    const dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)(NT / (TNW * NH)), (unsigned)B);
-    // more than 64 KiB of dynamic LDS needs the attribute; set per launch (it is per device, and cheap)
-    if constexpr (PC) {
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void *)conv2d_mfma_pc<TM, TNW, NH, NU>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return (int)e;
-        }
-        hipLaunchKernelGGL((conv2d_mfma_pc<TM, TNW, NH, NU>), grid, dim3(THREADS * NH + THREADS), lds, stream, in, wp, scale,
-                           shift, y, Cout, H, W, KT, dil, relu, nchunk, NT, tiles_x, tail8, shuf);
-    } else {
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void *)conv2d_mfma<TM, TNW, NH, NU>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return (int)e;
-        }
-        hipLaunchKernelGGL((conv2d_mfma<TM, TNW, NH, NU>), grid, dim3(THREADS * NH), lds, stream, in, wp, scale, shift, y,
-                           Cout, H, W, KT, dil, relu, nchunk, NT, tiles_x, tail8, shuf);
-    }
-    return decnet_launch_status();
+    if constexpr (PC)
+        return conv2d_mfma_launch(conv2d_mfma_pc<TM, TNW, NH, NU>, THREADS * NH + THREADS, lds, TM, NT / (TNW * NH), in, wp,
+                                  scale, shift, y, B, Cout, H, W, KT, dil, relu, nchunk, NT, shuf, stream);
+    else
+        return conv2d_mfma_launch(conv2d_mfma<TM, TNW, NH, NU>, THREADS * NH, lds, TM, NT / (TNW * NH), in, wp, scale,
+                                  shift, y, B, Cout, H, W, KT, dil, relu, nchunk, NT, shuf, stream);
 }
 
 template <int TNW, int NH, bool PC>
@@ -591,45 +455,21 @@ int launch_tm(int tm, const Segs &in, const i32x4 *wp, const float *scale, const
 
 }  // namespace
 
-extern "C" {
-
-size_t decnet_conv2d_mfma_packed_bytes_acc2(int Cin, int Cout, int k) {
+// ---- what conv2d_mfma.hip's entry points call under DECNET_CONV2D_ACC=2 (declared in conv2d_mfma_common.h) ---------------
+size_t conv2d_mfma_packed_bytes_acc2(int Cin, int Cout, int k) {
     if (Cin < 1 || Cout < 1 || (k != 1 && k != 3)) return 0;
     const size_t blocks = (size_t)ceil_div(Cin, 16) * (k * k) * 2 + 2;       // + 2: the prefetch runs one (chunk, tap) ahead
     return blocks * padded_nt(Cout) * 64 * 16;
 }
 
-static int pack_impl(const float *w, void *w_packed, int Cin, int Cout, int k, int tr, void *stream) {
-    if (!w || !w_packed) return DECNET_ERR_NULL_POINTER;
-    const size_t bytes = decnet_conv2d_mfma_packed_bytes_acc2(Cin, Cout, k);
-    if (!bytes) return DECNET_ERR_UNSUPPORTED;
-    const int NT = padded_nt(Cout);
+int conv2d_mfma_pack_acc2(const float *w, void *w_packed, int Cin, int Cout, int k, int tr, void *stream) {
     const int nchunk = ceil_div(Cin, 16);
-    const long total = (long)nchunk * (k * k) * 2 * NT * 64;
-    hipError_t e = hipMemsetAsync((char *)w_packed + (size_t)total * 16, 0, bytes - (size_t)total * 16,
-                                  (hipStream_t)stream);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(conv2d_mfma_pack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w,
-                       (i32x4 *)w_packed, Cin, Cout, k * k, NT, total, tr, nchunk, Cin - 16 * (nchunk - 1) <= 8 ? 1 : 0);
-    return decnet_launch_status();
+    return conv2d_mfma_pack_launch(conv2d_mfma_pack, w, w_packed, conv2d_mfma_packed_bytes_acc2(Cin, Cout, k), Cin, Cout,
+                                   k * k, padded_nt(Cout), 2, tr, stream, nchunk, Cin - 16 * (nchunk - 1) <= 8 ? 1 : 0);
 }
 
-int decnet_conv2d_mfma_pack_weight_acc2(const float *w, void *w_packed, int Cin, int Cout, int k, void *stream) {
-    return pack_impl(w, w_packed, Cin, Cout, k, 0, stream);
-}
-
-size_t decnet_deconv2d_mfma_packed_bytes_acc2(int Cin, int Cout) {
-    if (Cout < 1 || Cout > 7281) return 0;
-    return decnet_conv2d_mfma_packed_bytes_acc2(Cin, 9 * Cout, 1);
-}
-
-int decnet_deconv2d_mfma_pack_weight_acc2(const float *w, void *w_packed, int Cin, int Cout, void *stream) {
-    if (Cout < 1 || Cout > 7281) return DECNET_ERR_UNSUPPORTED;
-    return pack_impl(w, w_packed, Cin, 9 * Cout, 1, 1, stream);
-}
-
-static int run_impl(const Segs &in, long Cin, const void *w_packed, const float *scale, const float *shift, float *y,
-                    int B, int Cout, int H, int W, int k, int dilation, int relu, int shuf, void *stream) {
+int conv2d_mfma_run_acc2(const Segs &in, long Cin, const void *w_packed, const float *scale, const float *shift, float *y,
+                         int B, int Cout, int H, int W, int k, int dilation, int relu, int shuf, void *stream) {
     if (B > 65535 || Cin > 65536 || (double)H * W >= 2147483648.0 / (shuf ? 9 : 1)) return DECNET_ERR_UNSUPPORTED;
     const int TN = pick_tn(Cout), NT = padded_nt(Cout), nchunk = ceil_div((int)Cin, 16);
     if (NT / TN > 65535 || (double)ceil_div(W, 16) * ceil_div(H, 8) >= 2.0e9) return DECNET_ERR_UNSUPPORTED;
@@ -658,36 +498,3 @@ static int run_impl(const Segs &in, long Cin, const void *w_packed, const float 
 #undef GO
     return DECNET_ERR_UNSUPPORTED;
 }
-
-int decnet_conv2d_mfma_cat_bn_act_acc2(const float *const *xs, const int *cins, int nseg, const void *w_packed,
-                                  const float *scale, const float *shift, float *y, int B, int Cout, int H, int W,
-                                  int k, int dilation, int relu, void *stream) {
-    if (!xs || !cins || !w_packed || !scale || !shift || !y) return DECNET_ERR_NULL_POINTER;
-    if (nseg < 1 || nseg > MAXSEG || (k != 1 && k != 3)) return DECNET_ERR_UNSUPPORTED;
-    if (B < 1 || Cout < 1 || H < 1 || W < 1 || dilation < 1) return DECNET_ERR_BAD_SHAPE;
-    Segs in{};
-    long Cin = 0;
-    for (int i = 0; i < nseg; ++i) {
-        if (!xs[i]) return DECNET_ERR_NULL_POINTER;
-        if (cins[i] < 1) return DECNET_ERR_BAD_SHAPE;
-        in.p[i] = xs[i];
-        in.c[i] = cins[i];
-        Cin += cins[i];
-    }
-    in.n = nseg;
-    return run_impl(in, Cin, w_packed, scale, shift, y, B, Cout, H, W, k, dilation, relu, 0, stream);
-}
-
-int decnet_deconv2d_mfma_k3s3_bn_act_acc2(const float *x, const void *w_packed, const float *scale, const float *shift,
-                                     float *y, int B, int Cin, int Cout, int H, int W, int relu, void *stream) {
-    if (!x || !w_packed || !scale || !shift || !y) return DECNET_ERR_NULL_POINTER;
-    if (B < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1) return DECNET_ERR_BAD_SHAPE;
-    if (Cout > 7281) return DECNET_ERR_UNSUPPORTED;
-    Segs in{};
-    in.p[0] = x;
-    in.c[0] = Cin;
-    in.n = 1;
-    return run_impl(in, Cin, w_packed, scale, shift, y, B, 9 * Cout, H, W, 1, 1, relu, Cout, stream);
-}
-
-}  // extern "C"
