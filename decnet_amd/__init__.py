@@ -8,7 +8,9 @@
 * hip_grad(): opt-in backward of the few-channel stride-1 conv units with frozen BatchNorm (Conv2dSmallFunction): the
   weight gradient as a deterministic fp32 matrix-core reduction, dx on the forward kernel with flipped weights; and of
   the full-resolution tail (WarpDisparityFunction, Unfold3CatFunction, DynamicUpsample3Function, SigmoidBlendFunction):
-  the inference entries forward, fixed-order gathers backward; and of stage 0 (Conv3dFunction, CostVolumeFunction: the
+  the inference entries forward, fixed-order gathers backward; the detail maps and soft masks a training forward keeps
+  (SquaredDiffFunction, DetailTailFunction, SigmoidBlendSoftFunction: GenerateSparseMask.detail, SoftAttention.fuse with
+  want_soft); and of stage 0 (Conv3dFunction, CostVolumeFunction: the
   eight Conv3d units of CostRegNetNoDown, the per-layer inference entries forward; BatchNorm3d frozen, or in .train()
   mode on the statistics of the batch: BatchNorm3dActFunction, the Columns layout of csrc/batchnorm.hip)
 
@@ -24,8 +26,8 @@ from .ops import spamatvar_forward, spamatvar_forward_bits  # noqa: F401
 from .engine import StereoEngine  # noqa: F401
 from .loss import Loss, StageLossFunction  # noqa: F401
 from .conv2d_grad import Conv2dSmallFunction, hip_grad, hip_grad_enabled  # noqa: F401
-from .tail_grad import (DynamicUpsample3Function, SigmoidBlendFunction, Unfold3CatFunction,  # noqa: F401
-                        WarpDisparityFunction)
+from .tail_grad import (DetailTailFunction, DynamicUpsample3Function, SigmoidBlendFunction,  # noqa: F401
+                        SigmoidBlendSoftFunction, SquaredDiffFunction, Unfold3CatFunction, WarpDisparityFunction)
 from .stage0_grad import BatchNorm3dActFunction, Conv3dFunction, CostVolumeFunction  # noqa: F401
 from .stage0 import (CostRegNetNoDown, GetCostVolume, Stage0, disparity_regression,  # noqa: F401
                      drop_weight_caches, get_disp_samples)
@@ -35,4 +37,4 @@ __all__ = ["SpaMat", "SpaVar", "SpaMatFunction", "SpaVarFunction", "spamatvar_fo
            "Stage0", "DecnetHipError", "version", "drop_weight_caches", "StereoEngine", "Loss",
            "StageLossFunction", "Conv2dSmallFunction", "hip_grad", "hip_grad_enabled", "WarpDisparityFunction",
            "Unfold3CatFunction", "DynamicUpsample3Function", "SigmoidBlendFunction", "Conv3dFunction", "CostVolumeFunction",
-           "BatchNorm3dActFunction"]
+           "BatchNorm3dActFunction", "SquaredDiffFunction", "DetailTailFunction", "SigmoidBlendSoftFunction"]

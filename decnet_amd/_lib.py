@@ -60,6 +60,12 @@ SIGNATURES = {
     "decnet_fold3": [_P, _P] + [_I] * 4 + [_P],
     "decnet_sigmoid_blend": [_P] * 4 + [_Z, _P],
     "decnet_sigmoid_blend_backward": [_P] * 7 + [_Z, _P],
+    "decnet_sqdiff": [_P] * 3 + [_Z, _P],
+    "decnet_sqdiff_backward": [_P] * 5 + [_Z, _P],
+    "decnet_detail_tail": [_P, _F] + [_P] * 3 + [_I] * 3 + [_P],
+    "decnet_detail_tail_backward": [_P] * 3 + [_Z, _P],
+    "decnet_sigmoid_blend_soft": [_P] * 5 + [_Z, _P],
+    "decnet_sigmoid_blend_soft_backward": [_P] * 8 + [_Z, _P],
     "decnet_s2d3_pad1": [_P, _P] + [_I] * 4 + [_P],
     "decnet_d2s3_pad1": [_P, _P] + [_I] * 4 + [_P],
     "decnet_s2d3_pad0": [_P, _P] + [_I] * 4 + [_P],

@@ -23,7 +23,8 @@ import torch.nn.functional as F
 from . import ops2d
 from .conv2d_grad import (BatchNormActFunction, Conv2dMfmaFunction, Conv2dS3Function, Conv2dSmallFunction, Deconv2dS3Function,
                           hip_grad_enabled)
-from .tail_grad import DynamicUpsample3Function, SigmoidBlendFunction, Unfold3CatFunction, WarpDisparityFunction
+from .tail_grad import (DetailTailFunction, DynamicUpsample3Function, SigmoidBlendFunction, SigmoidBlendSoftFunction,
+                        SquaredDiffFunction, Unfold3CatFunction, WarpDisparityFunction)
 from ._lib import DecnetHipError, UNSUPPORTED
 from .ops import spamatvar_forward, spamatvar_forward_bits
 from .stage0 import (CachesWeights, CostRegNetNoDown, Stage0, cache_attrs, drop_weight_caches, fold_bn, fold_none,  # noqa: F401
@@ -85,17 +86,39 @@ def tail_grad_gate(*ts):
 
 
 def tail_grad_route(op, B, C, H, W, s=3, fea_hw=None):
-    """Whether `op` ("warp", "unfold", "upsample") runs as its tail_grad Function under ``hip_grad()``: the shape limits
-    of the inference route of the same op, decided with the switches at their defaults (as Unit._grad_route).  A function
-    of sizes alone: no tensor, no GPU.  warp: right [B,C,H,W]; unfold: fea [B,C,*fea_hw], disp [B,H,W], down-scale s;
-    upsample: disp [B,H,W] (C is not looked at)."""
+    """Whether `op` ("warp", "unfold", "upsample", "sqdiff", "detail") runs as its tail_grad Function under ``hip_grad()``:
+    the shape limits of the inference route of the same op, decided with the switches at their defaults (as
+    Unit._grad_route).  A function of sizes alone: no tensor, no GPU.  warp: right [B,C,H,W]; unfold: fea [B,C,*fea_hw],
+    disp [B,H,W], down-scale s; upsample: disp [B,H,W] (C is not looked at); sqdiff: two tensors [B,C,H,W] (the flat
+    entry's 2^40 floats); detail: logits [B,H,W] (C is not looked at; the limits of decnet_detail_mask) -- both less the
+    sizes measured slower than the torch ops they replace (_detail_slower)."""
     if op == "warp":
         return H > 1 and W > 1 and H <= 65535
     if op == "unfold":
         return s == 3 and H <= 65535 and B * (C + 1) <= 65535 and tuple(fea_hw) == (3 * H, 3 * W)
     if op == "upsample":
         return s == 3 and H <= 65535
+    if op == "sqdiff":
+        return 1 <= B * C * H * W <= 1 << 40 and not _detail_slower(B * H * W)
+    if op == "detail":
+        return (1 <= B <= 65535 and 1 <= H <= 65535 and 1 <= W <= 1 << 28 and
+                float(B) * H * ((W + 1023) // 1024) < 2.0e9 and not _detail_slower(B * H * W))
     raise ValueError("no such op: %s" % op)
+
+
+def _detail_slower(n):
+    """The sizes (n = B H W, the pixels of the detail map over the batch) at which GenerateSparseMask.detail keeps its tail
+    in torch ops under ``hip_grad()``: those where forward + backward through SquaredDiffFunction and DetailTailFunction was
+    measured slower than the same module with `d * d`, sigmoid, clone and two masked fills -- eager, B = 4, one run
+    (tools/bench_detail_grad.py, profiles/detail_grad.json; torch's time over ours, in brackets as GraphedStep replays).
+      * n = 4 x 60 x 108 = 25920: train mode 0.95 (1.04), eval mode 1.03 (1.02); n = 4 x 180 x 324 = 233280: 0.98 (1.01) and
+        0.98 (1.03).  An eager step of the generator is bound by the host there (0.92 - 1.44 ms whatever the size: dozens
+        of small launches), and two Function calls through ctypes cost the host more than the ten torch ops they replace; the kernels
+        themselves win (every replay is faster).  The eager verdict decides, as for _bn_train_slower, and is carried up to the
+        next measured size.
+      * n = 4 x 540 x 972 = 2099520: 1.00 (1.02) and 1.01 (1.02): from there on the Functions.
+    Below 25920 pixels nothing is excluded (nothing was measured there): the tests run there."""
+    return 25920 <= n < 2099520
 
 
 def _mfma_grad_slower(cin, cout, hw):
@@ -724,6 +747,39 @@ class GenerateSparseMask(CachesWeights, nn.Module):
                                       thold, want_bits)
         return (out, bits) if want_bits else out
 
+    def detail(self, cur, pre, thold, want_bits=False):
+        """What the training forward keeps of a mask generator (SparseDenseNetRefinementMask.py:148-170) ->
+        (prob, mask, bits): prob [B,H,W] = sigmoid(self(cur, pre)), with its autograd graph where autograd is on; mask =
+        (prob > thold) as a float 0/1 plane without a graph (the reference thresholds under no_grad); bits: the mask as the
+        bit-packed copy the SpaMat kernels read where want_bits is set and a HIP route ran, else None.
+
+        Under ``hip_grad()`` with autograd on, in either BatchNorm mode: the units take their own routes, the squared
+        difference is SquaredDiffFunction and sigmoid, threshold and bit plane are DetailTailFunction
+        (csrc/detail_grad.hip).  Under ``no_grad`` in eval mode on the GPU: the one launch of mask() with its logits kept,
+        and decnet_detail_tail for prob -- mask and bits are exactly mask()'s.  Otherwise torch ops.
+
+        The composed ``hip_grad()`` route and the fused inference kernel order their arithmetic differently (separate
+        convolutions with BatchNorm applied per layer against one fma chain with BatchNorm folded), so their masks may
+        disagree on pixels whose probability is within rounding of thold."""
+        if tail_grad_gate(cur, pre):
+            c3, p3 = self.conv_sub(cur), self.deconv(pre)
+            if c3.shape == p3.shape and tail_grad_gate(c3, p3) and tail_grad_route("sqdiff", *c3.shape):
+                d2 = SquaredDiffFunction.apply(c3, p3)
+            else:
+                d = c3 - p3
+                d2 = d * d
+            logits = self.conv(d2).squeeze(1)
+            if tail_grad_gate(logits) and tail_grad_route("detail", logits.shape[0], 1, *logits.shape[-2:]):
+                return DetailTailFunction.apply(logits, thold, want_bits)
+            prob = torch.sigmoid(logits)
+            return prob, (prob.detach() > thold).to(prob.dtype), None
+        if hip_gate(cur, self.training) and cur.shape[-2] <= 65535:
+            mask, bits, logits = ops2d.detail_mask(self.conv_sub(cur).contiguous(), self.deconv(pre).contiguous(),
+                                                   self._host_params(), thold, want_bits, want_logits=True)
+            return ops2d.detail_tail(logits, thold, True, False, False)[0], mask, bits
+        prob = torch.sigmoid(self(cur, pre))
+        return prob, (prob.detach() > thold).to(prob.dtype), None
+
 
 class DynamicUpsampling(nn.Module):
     """submodule.py:566-589: x3 upsampling of a disparity map with per-pixel softmax weights over
@@ -770,15 +826,17 @@ class SoftAttention(nn.Module):
     def forward(self, x):
         return torch.sigmoid(self.conv(x))
 
-    def fuse(self, fea, dense, sparse, mask, var):
+    def fuse(self, fea, dense, sparse, mask, var, want_soft=False):
         """The attention and the fusion of the stage loop (SparseDenseNetRefinementMask.py:195-202) in one go:
         soft = self(cat(fea, dense, sparse, mask, -var)); dense * (1 - soft) + soft * sparse.  On the GPU the
         concatenation, the negation (folded into the first layer's weights), the sigmoid and the blend are part
-        of the three convolution launches."""
+        of the three convolution launches.
+        want_soft: -> (fused, soft), the soft mask the training loss reads; fused keeps the bits of the call without it
+        (on the HIP routes the last unit then runs without its epilogue, and one pass writes both planes)."""
         parts = (fea, dense.unsqueeze(1), sparse.unsqueeze(1), mask.unsqueeze(1), var.unsqueeze(1))
         u0, u1, u2 = self.conv[0], self.conv[1], self.conv[2]
         if u2.conv.out_channels == 1 and not u2.relu and tail_grad_gate(*parts):
-            y = self._fuse_grad(parts, dense, sparse)
+            y = self._fuse_grad(parts, dense, sparse, want_soft)
             if y is not None:
                 return y
         k0 = u0._hip_kind(parts)
@@ -789,11 +847,16 @@ class SoftAttention(nn.Module):
                 t = u0._forward_hip(parts[:4] + (-var.unsqueeze(1),), "mfma")
             t = u1(t)
             if u2._hip_kind(t) == "conv":
+                if want_soft:                           # the convolution of the epilogue entry, then the epilogue's statements
+                    o = u2._forward_hip((t,), "conv").squeeze(1)
+                    return ops2d.sigmoid_blend_soft(o, dense.contiguous(), sparse.contiguous())
                 return u2._forward_hip(t, "conv", epi=1, ea=dense.contiguous(), eb=sparse.contiguous()).squeeze(1)
             soft = torch.sigmoid(u2(t)).squeeze(1)
-            return dense * (1 - soft) + soft * sparse
+            fused = dense * (1 - soft) + soft * sparse
+            return (fused, soft) if want_soft else fused
         soft = self(parts[:4] + (-var.unsqueeze(1),)).squeeze(1)
-        return dense * (1 - soft) + soft * sparse
+        fused = dense * (1 - soft) + soft * sparse
+        return (fused, soft) if want_soft else fused
 
     def _fuse_grad_route(self, B, H, W):
         """Whether fuse() under ``hip_grad()`` runs its three units as Conv2dSmallFunctions (the variance negated as a
@@ -810,9 +873,9 @@ class SoftAttention(nn.Module):
         return (u2.conv.out_channels == 1 and not u2.relu and route(u0, 5) == "conv" and route(u1) == "conv" and
                 route(u2) == "conv")
 
-    def _fuse_grad(self, parts, dense, sparse):
+    def _fuse_grad(self, parts, dense, sparse, want_soft=False):
         """fuse() on the route of _fuse_grad_route (_fuse_grad_route_train in ``.train()`` mode); None where it does not
-        hold (the caller goes on as it always did)."""
+        hold (the caller goes on as it always did).  want_soft: (fused, soft) from SigmoidBlendSoftFunction."""
         B, _, H, W = parts[0].shape
         train = self.training
         if any(u.training != train or (train and u.bn is not None and not u.bn.training) for u in self.conv):
@@ -830,6 +893,8 @@ class SoftAttention(nn.Module):
                     del TALLY[n_tally:]
                 return None
             t = y
+        if want_soft:
+            return SigmoidBlendSoftFunction.apply(t.squeeze(1), dense, sparse)
         return SigmoidBlendFunction.apply(t.squeeze(1), dense, sparse)
 
 

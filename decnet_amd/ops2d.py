@@ -402,23 +402,91 @@ def sigmoid_blend_backward(o, a, b, gout, want_a=True, want_b=True):
     return go, ga, gb
 
 
+# ---- detail maps and soft masks under hip_grad() (csrc/detail_grad.hip; the Functions are in tail_grad.py) ---------------
+def sqdiff(a, b, out=None):
+    """(a - b) * (a - b) over tensors of one shape, torch's bits."""
+    _chk("b", b, _chk("a", a).shape)
+    return _run("decnet_sqdiff", (a, b), out, a.shape, a.numel())
+
+
+def sqdiff_backward(a, b, gout, want_a=True, want_b=True):
+    """-> (g_a or None, g_b or None): 2 gout (a - b) and its negative."""
+    _chk("gout", gout, _chk("b", b, _chk("a", a).shape).shape)
+    if not (want_a or want_b):
+        return None, None
+    ga = torch.empty_like(a) if want_a else None
+    gb = torch.empty_like(a) if want_b else None
+    _call("decnet_sqdiff_backward", a, a.data_ptr(), b.data_ptr(), gout.data_ptr(), ga.data_ptr() if want_a else None,
+          gb.data_ptr() if want_b else None, a.numel())
+    return ga, gb
+
+
+def detail_tail(logits, thold, want_prob=True, want_mask=True, want_bits=False):
+    """logits [B,H,W] -> (prob = sigmoid(logits), mask = prob > thold as float 0/1, bits: the mask as 64 pixels per int64
+    word), each None unless asked for."""
+    B, H, W = _chk("logits", logits).shape
+    if not (want_prob or want_mask or want_bits):
+        return None, None, None
+    prob = torch.empty_like(logits) if want_prob else None
+    mask = torch.empty_like(logits) if want_mask else None
+    bits = torch.empty((B, H, (W + 63) // 64), dtype=torch.int64, device=logits.device) if want_bits else None
+    _call("decnet_detail_tail", logits, logits.data_ptr(), float(thold), prob.data_ptr() if want_prob else None,
+          mask.data_ptr() if want_mask else None, bits.data_ptr() if want_bits else None, B, H, W)
+    return prob, mask, bits
+
+
+def detail_tail_backward(logits, g_prob):
+    """-> g_logits = g_prob * s * (1 - s), s = sigmoid(logits) as detail_tail computes it."""
+    _chk("g_prob", g_prob, _chk("logits", logits).shape)
+    gl = torch.empty_like(logits)
+    _call("decnet_detail_tail_backward", logits, logits.data_ptr(), g_prob.data_ptr(), gl.data_ptr(), logits.numel())
+    return gl
+
+
+def sigmoid_blend_soft(o, a, b):
+    """-> (sigmoid_blend(o, a, b), sigmoid(o)): the blend's bits, and the soft mask it was made with."""
+    _chk("b", b, _chk("a", a, _chk("o", o).shape).shape)
+    out, soft = torch.empty_like(o), torch.empty_like(o)
+    _call("decnet_sigmoid_blend_soft", o, o.data_ptr(), a.data_ptr(), b.data_ptr(), out.data_ptr(), soft.data_ptr(),
+          o.numel())
+    return out, soft
+
+
+def sigmoid_blend_soft_backward(o, a, b, gout, gsoft, want_a=True, want_b=True):
+    """gout, gsoft: the gradients of the two outputs, one of them may be None -> (g_o, g_a or None, g_b or None)."""
+    for n, t in (("a", a), ("b", b), ("gout", gout), ("gsoft", gsoft)):
+        if t is not None:
+            _chk(n, t, _chk("o", o).shape)
+    if gout is None and gsoft is None:
+        raise ValueError("gout and gsoft are both None")
+    go = torch.empty_like(o)
+    ga = torch.empty_like(o) if want_a else None
+    gb = torch.empty_like(o) if want_b else None
+    _call("decnet_sigmoid_blend_soft_backward", o, o.data_ptr(), a.data_ptr(), b.data_ptr(), _opt("gout", gout),
+          _opt("gsoft", gsoft), go.data_ptr(), ga.data_ptr() if want_a else None, gb.data_ptr() if want_b else None,
+          o.numel())
+    return go, ga, gb
+
+
 def detail_mask_params(flat):
     """The 92 folded host values of GenerateSparseMask.conv as the entry takes them: w3x3, scale3, shift3, w1x1, s1, b1."""
     arr = lambda v: (ctypes.c_float * len(v))(*v)  # noqa: E731
     return arr(flat[0:81]), arr(flat[81:84]), arr(flat[84:87]), arr(flat[87:90]), flat[90], flat[91]
 
 
-def detail_mask(cur3, pre3, params, thold, want_bits=False, out=None):
-    """-> (mask [B,H,W] float 0/1, bits: None or the bit-packed copy the SpaMat kernels read, 64 pixels per int64 word)."""
+def detail_mask(cur3, pre3, params, thold, want_bits=False, out=None, want_logits=False):
+    """-> (mask [B,H,W] float 0/1, bits: None or the bit-packed copy the SpaMat kernels read, 64 pixels per int64 word);
+    with want_logits -> (mask, bits, logits [B,H,W]: `detail` before the sigmoid)."""
     B, C, H, W = _chk("cur3", cur3).shape
     _chk("pre3", pre3, (B, 3, H, W))
     if C != 3:
         raise ValueError("cur3 has %d channels, the layer takes 3" % C)
     y = torch.empty((B, H, W), dtype=_F32, device=cur3.device) if out is None else _chk("out", out, (B, H, W))
     bits = torch.empty((B, H, (W + 63) // 64), dtype=torch.int64, device=cur3.device) if want_bits else None
-    _call("decnet_detail_mask", cur3, cur3.data_ptr(), pre3.data_ptr(), *params, float(thold), y.data_ptr(), None,
-          bits.data_ptr() if want_bits else None, B, H, W)
-    return y, bits
+    logits = torch.empty((B, H, W), dtype=_F32, device=cur3.device) if want_logits else None
+    _call("decnet_detail_mask", cur3, cur3.data_ptr(), pre3.data_ptr(), *params, float(thold), y.data_ptr(),
+          logits.data_ptr() if want_logits else None, bits.data_ptr() if want_bits else None, B, H, W)
+    return (y, bits, logits) if want_logits else (y, bits)
 
 
 # ---- stage 0 (channels-last [B,D,H,W,C] volumes; the activation buffers are flat, grow-only workspaces) ------------------

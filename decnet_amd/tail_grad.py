@@ -1,5 +1,6 @@
 """Forward and backward of the full-resolution tail on HIP under ``hip_grad()``: the warp of Refinement, the head and the
-tail of DynamicUpsampling and SoftAttention's sigmoid + blend (csrc/tail_grad.hip).
+tail of DynamicUpsampling and SoftAttention's sigmoid + blend (csrc/tail_grad.hip); the squared difference and the sigmoid /
+threshold tail of GenerateSparseMask's detail map, and the blend that also hands out its soft mask (csrc/detail_grad.hip).
 
 Each Function runs the entry that inference runs (``decnet_warp_disparity``, ``decnet_unfold3_cat``,
 ``decnet_dynamic_upsample3``; the blend is the statement sequence of ``decnet_conv2d_cat_epilogue``'s epilogue 1), so a
@@ -109,4 +110,68 @@ class SigmoidBlendFunction(Function):
         if not (want_o or want_a or want_b):
             return None, None, None
         go, ga, gb = ops2d.sigmoid_blend_backward(o, a, b, gout.contiguous(), want_a, want_b)
+        return (go if want_o else None), ga, gb
+
+
+class SquaredDiffFunction(Function):
+    """apply(a, b) -> (a - b) * (a - b), tensors of one shape (decnet_sqdiff): torch's bits, forward and backward."""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        a, b = a.contiguous(), b.contiguous()
+        ctx.save_for_backward(a, b)
+        return ops2d.sqdiff(a, b)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        a, b = ctx.saved_tensors
+        want_a, want_b = ctx.needs_input_grad
+        if not (want_a or want_b):
+            return None, None
+        return ops2d.sqdiff_backward(a, b, gout.contiguous(), want_a, want_b)
+
+
+class DetailTailFunction(Function):
+    """apply(logits [B,H,W], thold, want_bits) -> (prob = sigmoid(logits), mask = prob > thold as float 0/1, bits: the mask
+    as 64 pixels per int64 word, or None) (decnet_detail_tail).  Only ``prob`` carries a gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, thold, want_bits):
+        logits = logits.contiguous()
+        ctx.save_for_backward(logits)
+        prob, mask, bits = ops2d.detail_tail(logits, thold, True, True, bool(want_bits))
+        ctx.mark_non_differentiable(*((mask,) if bits is None else (mask, bits)))
+        return prob, mask, bits
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_prob, g_mask, g_bits):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        logits, = ctx.saved_tensors
+        return ops2d.detail_tail_backward(logits, g_prob.contiguous()), None, None
+
+
+class SigmoidBlendSoftFunction(Function):
+    """apply(o, a, b) -> (a * (1 - s) + s * b, s), s = sigmoid(o) (decnet_sigmoid_blend_soft): SigmoidBlendFunction's blend,
+    bit for bit, and the soft mask beside it.  An output that nobody differentiates costs no gradient tensor."""
+
+    @staticmethod
+    def forward(ctx, o, a, b):
+        o, a, b = o.contiguous(), a.contiguous(), b.contiguous()
+        ctx.save_for_backward(o, a, b)
+        ctx.set_materialize_grads(False)
+        return ops2d.sigmoid_blend_soft(o, a, b)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout, gsoft):
+        o, a, b = ctx.saved_tensors
+        want_o, want_a, want_b = ctx.needs_input_grad
+        if (gout is None and gsoft is None) or not (want_o or want_a or want_b):
+            return None, None, None
+        want_a, want_b = want_a and gout is not None, want_b and gout is not None       # (the soft mask does not read them)
+        go, ga, gb = ops2d.sigmoid_blend_soft_backward(o, a, b, None if gout is None else gout.contiguous(),
+                                                       None if gsoft is None else gsoft.contiguous(), want_a, want_b)
         return (go if want_o else None), ga, gb

@@ -538,6 +538,38 @@ int decnet_fold3(const float *g, float *g_fea, int B, int C, int h, int w, void 
 int decnet_sigmoid_blend(const float *o, const float *a, const float *b, float *out, size_t n, void *stream);
 int decnet_sigmoid_blend_backward(const float *o, const float *a, const float *b, const float *gout, float *g_o,
                                   float *g_a, float *g_b, size_t n, void *stream);
+/* ---- detail maps and soft masks under hip_grad() (csrc/detail_grad.hip) -------------------------------------------------
+ * What a training forward keeps beside the disparities: sigmoid(detail) of GenerateSparseMask with its thresholded copies,
+ * and SoftAttention's soft mask next to its blend.  Common to all: elementwise fp32, contraction off; planes at any float
+ * alignment (the values do not depend on it); no allocation, no synchronisation (capturable); nothing is launched and
+ * nothing is written on any refusal.  The flat entries take n floats, 1 <= n <= 2^40 (else DECNET_ERR_BAD_SHAPE /
+ * DECNET_ERR_UNSUPPORTED).
+ *
+ * decnet_sqdiff: d = a - b, out = d d, each rounded once: the bits of torch's (a - b) * (a - b).
+ * decnet_sqdiff_backward: t = gout d, g_a = t + t, g_b = -g_a: the bits of torch autograd through d * d.  g_a, g_b: each may
+ * be NULL, not both. */
+int decnet_sqdiff(const float *a, const float *b, float *out, size_t n, void *stream);
+int decnet_sqdiff_backward(const float *a, const float *b, const float *gout, float *g_a, float *g_b, size_t n,
+                           void *stream);
+/* decnet_detail_tail: logits [B,H,W] (`detail`, e.g. what decnet_detail_mask wrote) -> s = 1 / (1 + expf(-z)), the
+ * statement of decnet_detail_mask;
+ *   prob   NULL or [B,H,W]: s
+ *   mask   NULL or [B,H,W]: s > thold ? 1 : 0
+ *   bits   NULL or [B,H,ceil(W/64)] 64-bit words, bit i of word w = pixel 64 w + i of the row, zero at and past W
+ * (not all three NULL).  Limits as decnet_detail_mask.
+ * decnet_detail_tail_backward over n floats: g_logits = g_prob (s (1 - s)), s recomputed as the forward computes it; a
+ * saturated sigmoid gives exactly 0, never NaN. */
+int decnet_detail_tail(const float *logits, float thold, float *prob, float *mask, unsigned long long *bits, int B, int H,
+                       int W, void *stream);
+int decnet_detail_tail_backward(const float *logits, const float *g_prob, float *g_logits, size_t n, void *stream);
+/* decnet_sigmoid_blend_soft: out as decnet_sigmoid_blend writes it (the same statements, the same bits), soft = s.
+ * decnet_sigmoid_blend_soft_backward: g_o = (gout (b - a) + gsoft) (s (1 - s)), g_a = gout (1 - s), g_b = gout s.  gout,
+ * gsoft: each may be NULL, not both; without gsoft the three results have the bits of decnet_sigmoid_blend_backward, without
+ * gout g_o = gsoft (s (1 - s)) and g_a, g_b are written as zeros.  g_a, g_b: each may be NULL. */
+int decnet_sigmoid_blend_soft(const float *o, const float *a, const float *b, float *out, float *soft, size_t n,
+                              void *stream);
+int decnet_sigmoid_blend_soft_backward(const float *o, const float *a, const float *b, const float *gout,
+                                       const float *gsoft, float *g_o, float *g_a, float *g_b, size_t n, void *stream);
 /* Space-to-depth in front of the stride-3 convolutions of FeatExtNetChannelPlus (Conv2d k 3, stride 3, padding 1,
  * submodule.py:270-300): x [B,C,H,W] -> out [B,9C,Ho,Wo], Ho = (H-1)/3+1, Wo = (W-1)/3+1,
  * out[b,c*9+ky*3+kx,yo,xo] = x[b,c,3yo-1+ky,3xo-1+kx] (0 outside); the convolution is then the 1 x 1 convolution with the
