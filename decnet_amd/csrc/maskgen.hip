@@ -11,7 +11,7 @@
 // thread; the 81 + 3 weights and the folded BatchNorm constants are wave-uniform scalar loads; outputs are the float mask and, optionally,
 // the logits (for callers that want `detail`) and a bit-packed copy (one 64-bit word per 64 pixels of a
 // row, bit i = pixel 64 w + i) for consumers that do not need 4 bytes per pixel.
-#include "common.h"
+#include "pointwise.h"
 
 namespace {
 
@@ -23,16 +23,6 @@ struct MaskGenParams {
 };
 
 typedef int i32x4_g __attribute__((ext_vector_type(4)));
-
-// bit i of a 16-bit value -> bit 4 i of a 64-bit word
-__device__ __forceinline__ unsigned long long spread4(unsigned long long x) {
-    x &= 0xffffull;
-    x = (x | (x << 24)) & 0x000000ff000000ffull;
-    x = (x | (x << 12)) & 0x000f000f000f000full;
-    x = (x | (x << 6)) & 0x0303030303030303ull;
-    x = (x | (x << 3)) & 0x1111111111111111ull;
-    return x;
-}
 
 // Round 4: FOUR consecutive pixels per thread.  The first version (one pixel per thread) issued 54 dword loads per
 // pixel and ran at 0.11 ms for the 118 MB of a full-resolution launch -- bound by vector-memory INSTRUCTIONS, not
@@ -97,7 +87,7 @@ __global__ __launch_bounds__(256) void detail_mask(const float *__restrict__ cur
 #pragma unroll
         for (int co = 0; co < 3; ++co) z = fmaf(P.w1[co], fmaf(t[co][e], P.scale3[co], P.shift3[co]), z);
         z = fmaf(z, P.scale1, P.shift1);
-        const float s = 1.f / (1.f + expf(-z));                            // torch.sigmoid
+        const float s = sigmoid_f(z);
         on[e] = x0 + e < W && s > P.thold;                                 // mask[m > thold] = 1, else 0
         zv[e] = z;
         mv[e] = on[e] ? 1.f : 0.f;
@@ -117,17 +107,7 @@ __global__ __launch_bounds__(256) void detail_mask(const float *__restrict__ cur
                 }
         }
     }
-    if (bits) {
-        const unsigned long long b0 = __ballot(on[0]), b1 = __ballot(on[1]), b2 = __ballot(on[2]), b3 = __ballot(on[3]);
-        const int lane = threadIdx.x & 63;
-        if ((lane & 15) == 0) {                                            // lanes 0, 16, 32, 48: one word each
-            const int sh = lane;                                           // 16 w
-            const unsigned long long word = spread4(b0 >> sh) | (spread4(b1 >> sh) << 1) | (spread4(b2 >> sh) << 2) |
-                                            (spread4(b3 >> sh) << 3);
-            const int wi = x0 >> 6;                                        // word of pixel x0 = 64-aligned block
-            if (wi < words_per_row) bits[((size_t)b * H + y) * words_per_row + wi] = word;
-        }
-    }
+    if (bits) pack_mask_bits(on, x0, (size_t)b * H + y, words_per_row, bits);
 }
 
 }  // namespace
@@ -137,8 +117,7 @@ extern "C" int decnet_detail_mask(const float *cur3, const float *pre3, const fl
                                   float thold, float *mask, float *logits, unsigned long long *bits, int B,
                                   int H, int W, void *stream) {
     if (!cur3 || !pre3 || !w3x3 || !scale3 || !shift3 || !w1x1 || !mask) return DECNET_ERR_NULL_POINTER;
-    if (B < 1 || H < 1 || W < 1 || B > 65535 || H > 65535) return DECNET_ERR_BAD_SHAPE;
-    if ((double)B * H * ceil_div(W, 1024) >= 2.0e9 || W > (1 << 28)) return DECNET_ERR_UNSUPPORTED;
+    if (int rc = row_refusal(B, H, W)) return rc;
     MaskGenParams P;                       // host arrays: 90 floats, passed by value as a kernel argument
     for (int i = 0; i < 81; ++i) (&P.w3[0][0][0][0])[i] = w3x3[i];
     for (int i = 0; i < 3; ++i) { P.scale3[i] = scale3[i]; P.shift3[i] = shift3[i]; P.w1[i] = w1x1[i]; }

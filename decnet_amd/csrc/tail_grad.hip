@@ -1,97 +1,11 @@
-// decnet_amd/csrc/tail_grad.hip -- the full-resolution tail under hip_grad(): backward of decnet_warp_disparity and
-// decnet_dynamic_upsample3, the inverse permutation of decnet_unfold3_cat, and SoftAttention's sigmoid + blend as a pass
-// of its own with its backward (decnet_amd/tail_grad.py).  Every gradient is a gather in a fixed order: no atomics, no
-// allocation, no synchronisation, the same bits on every run and under graph replay.  Planes are accepted at any float
-// alignment (the blend uses 16-byte accesses only where every plane is 16-byte aligned; the values do not depend on it).
-#include "common.h"
+// decnet_amd/csrc/tail_grad.hip -- the gathers of the full-resolution tail under hip_grad(): backward of
+// decnet_warp_disparity and decnet_dynamic_upsample3 and the inverse permutation of decnet_unfold3_cat
+// (decnet_amd/tail_grad.py; SoftAttention's sigmoid + blend is an elementwise pass, csrc/detail_grad.hip).  Every gradient
+// is a gather in a fixed order: no atomics, no allocation, no synchronisation, the same bits on every run and under graph
+// replay.  Planes are accepted at any float alignment.
+#include "pointwise.h"                                                   // aligned16
 
 namespace {
-
-// ---- SoftAttention's tail: s = sigmoid(o), out = a (1 - s) + s b ---------------------------------------------------------
-// The statement sequence of the epi == 1 branch of conv2d_small (csrc/conv2d_small.hip), contraction off: the same bits.
-__global__ __launch_bounds__(256) void sigmoid_blend(const float *__restrict__ o, const float *__restrict__ a,
-                                                     const float *__restrict__ b, float *__restrict__ out, size_t n,
-                                                     int vec) {
-#pragma clang fp contract(off)
-    const size_t i0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
-    if (i0 >= n) return;
-    const bool full = vec && i0 + 3 < n;
-    float vo[4], va[4], vb[4], r[4];
-    if (full) {
-        const float4 to = *reinterpret_cast<const float4 *>(o + i0), ta = *reinterpret_cast<const float4 *>(a + i0);
-        const float4 tb = *reinterpret_cast<const float4 *>(b + i0);
-        vo[0] = to.x; vo[1] = to.y; vo[2] = to.z; vo[3] = to.w;
-        va[0] = ta.x; va[1] = ta.y; va[2] = ta.z; va[3] = ta.w;
-        vb[0] = tb.x; vb[1] = tb.y; vb[2] = tb.z; vb[3] = tb.w;
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const size_t i = i0 + e < n ? i0 + e : i0;
-            vo[e] = o[i]; va[e] = a[i]; vb[e] = b[i];
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const float sft = 1.f / (1.f + expf(-vo[e]));
-        const float t1 = va[e] * (1.f - sft), t2 = sft * vb[e];
-        r[e] = t1 + t2;
-    }
-    if (full) {
-        *reinterpret_cast<float4 *>(out + i0) = make_float4(r[0], r[1], r[2], r[3]);
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            if (i0 + e < n) out[i0 + e] = r[e];
-    }
-}
-
-// g_o = gout (b - a) s (1 - s), g_a = gout (1 - s), g_b = gout s, with s recomputed from o as the forward computes it
-// (a saturated sigmoid gives s (1 - s) = 0 exactly: g_o = 0, never NaN).  g_a, g_b: may be NULL.
-__global__ __launch_bounds__(256) void sigmoid_blend_bwd(const float *__restrict__ o, const float *__restrict__ a,
-                                                         const float *__restrict__ b, const float *__restrict__ gout,
-                                                         float *__restrict__ g_o, float *__restrict__ g_a,
-                                                         float *__restrict__ g_b, size_t n, int vec) {
-#pragma clang fp contract(off)
-    const size_t i0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
-    if (i0 >= n) return;
-    const bool full = vec && i0 + 3 < n;
-    float vo[4], va[4], vb[4], vg[4], ro[4], ra[4], rb[4];
-    if (full) {
-        const float4 to = *reinterpret_cast<const float4 *>(o + i0), ta = *reinterpret_cast<const float4 *>(a + i0);
-        const float4 tb = *reinterpret_cast<const float4 *>(b + i0), tg = *reinterpret_cast<const float4 *>(gout + i0);
-        vo[0] = to.x; vo[1] = to.y; vo[2] = to.z; vo[3] = to.w;
-        va[0] = ta.x; va[1] = ta.y; va[2] = ta.z; va[3] = ta.w;
-        vb[0] = tb.x; vb[1] = tb.y; vb[2] = tb.z; vb[3] = tb.w;
-        vg[0] = tg.x; vg[1] = tg.y; vg[2] = tg.z; vg[3] = tg.w;
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const size_t i = i0 + e < n ? i0 + e : i0;
-            vo[e] = o[i]; va[e] = a[i]; vb[e] = b[i]; vg[e] = gout[i];
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const float sft = 1.f / (1.f + expf(-vo[e]));
-        const float om = 1.f - sft;
-        ro[e] = vg[e] * (vb[e] - va[e]) * (sft * om);
-        ra[e] = vg[e] * om;
-        rb[e] = vg[e] * sft;
-    }
-    if (full) {
-        *reinterpret_cast<float4 *>(g_o + i0) = make_float4(ro[0], ro[1], ro[2], ro[3]);
-        if (g_a) *reinterpret_cast<float4 *>(g_a + i0) = make_float4(ra[0], ra[1], ra[2], ra[3]);
-        if (g_b) *reinterpret_cast<float4 *>(g_b + i0) = make_float4(rb[0], rb[1], rb[2], rb[3]);
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            if (i0 + e < n) {
-                g_o[i0 + e] = ro[e];
-                if (g_a) g_a[i0 + e] = ra[e];
-                if (g_b) g_b[i0 + e] = rb[e];
-            }
-    }
-}
 
 // ---- inverse of unfold3_cat's feature part: g_fea[b,c,3y+i,3x+j] = g[b,1+9c+3i+j,y,x] ----------------------------------------
 __global__ __launch_bounds__(256) void fold3(const float *__restrict__ g, float *__restrict__ g_fea, int C, int h, int w) {
@@ -331,34 +245,11 @@ __global__ __launch_bounds__(256) void warp_disparity_gright(const float *__rest
     }
 }
 
-inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 constexpr int GRIGHT_MAX_W = (DECNET_LDS_BUDGET - 32) / 36;              // 1819: ix[W] + gout[8][W] in 64 KiB
 
 }  // namespace
 
 extern "C" {
-
-int decnet_sigmoid_blend(const float *o, const float *a, const float *b, float *out, size_t n, void *stream) {
-    if (!o || !a || !b || !out) return DECNET_ERR_NULL_POINTER;
-    if (n < 1) return DECNET_ERR_BAD_SHAPE;
-    if (n > ((size_t)1 << 40)) return DECNET_ERR_UNSUPPORTED;
-    const int vec = aligned16(o) && aligned16(a) && aligned16(b) && aligned16(out);
-    hipLaunchKernelGGL(sigmoid_blend, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream, o, a, b, out,
-                       n, vec);
-    return decnet_launch_status();
-}
-
-int decnet_sigmoid_blend_backward(const float *o, const float *a, const float *b, const float *gout, float *g_o,
-                                  float *g_a, float *g_b, size_t n, void *stream) {
-    if (!o || !a || !b || !gout || !g_o) return DECNET_ERR_NULL_POINTER;
-    if (n < 1) return DECNET_ERR_BAD_SHAPE;
-    if (n > ((size_t)1 << 40)) return DECNET_ERR_UNSUPPORTED;
-    const int vec = aligned16(o) && aligned16(a) && aligned16(b) && aligned16(gout) && aligned16(g_o) &&
-                    aligned16(g_a) && aligned16(g_b);                    // (NULL counts as aligned)
-    hipLaunchKernelGGL(sigmoid_blend_bwd, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream, o, a, b,
-                       gout, g_o, g_a, g_b, n, vec);
-    return decnet_launch_status();
-}
 
 int decnet_fold3(const float *g, float *g_fea, int B, int C, int h, int w, void *stream) {
     if (!g || !g_fea) return DECNET_ERR_NULL_POINTER;

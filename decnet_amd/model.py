@@ -85,6 +85,18 @@ def tail_grad_gate(*ts):
             all(t.is_cuda and t.dtype == torch.float32 for t in ts))
 
 
+def _tail_shape(op, B, C, H, W, s=3, fea_hw=None):
+    """The shapes the "warp", "unfold" and "upsample" entries take (arguments as tail_grad_route's): one answer for the
+    inference branch of the op and for its route under ``hip_grad()``."""
+    if op == "warp":
+        return H > 1 and W > 1 and H <= 65535
+    if op == "unfold":
+        return s == 3 and H <= 65535 and B * (C + 1) <= 65535 and tuple(fea_hw) == (3 * H, 3 * W)
+    if op == "upsample":
+        return s == 3 and H <= 65535
+    raise ValueError("no such op: %s" % op)
+
+
 def tail_grad_route(op, B, C, H, W, s=3, fea_hw=None):
     """Whether `op` ("warp", "unfold", "upsample", "sqdiff", "detail") runs as its tail_grad Function under ``hip_grad()``:
     the shape limits of the inference route of the same op, decided with the switches at their defaults (as
@@ -92,18 +104,12 @@ def tail_grad_route(op, B, C, H, W, s=3, fea_hw=None):
     disp [B,H,W], down-scale s; upsample: disp [B,H,W] (C is not looked at); sqdiff: two tensors [B,C,H,W] (the flat
     entry's 2^40 floats); detail: logits [B,H,W] (C is not looked at; the limits of decnet_detail_mask) -- both less the
     sizes measured slower than the torch ops they replace (_detail_slower)."""
-    if op == "warp":
-        return H > 1 and W > 1 and H <= 65535
-    if op == "unfold":
-        return s == 3 and H <= 65535 and B * (C + 1) <= 65535 and tuple(fea_hw) == (3 * H, 3 * W)
-    if op == "upsample":
-        return s == 3 and H <= 65535
     if op == "sqdiff":
         return 1 <= B * C * H * W <= 1 << 40 and not _detail_slower(B * H * W)
     if op == "detail":
         return (1 <= B <= 65535 and 1 <= H <= 65535 and 1 <= W <= 1 << 28 and
                 float(B) * H * ((W + 1023) // 1024) < 2.0e9 and not _detail_slower(B * H * W))
-    raise ValueError("no such op: %s" % op)
+    return _tail_shape(op, B, C, H, W, s, fea_hw)
 
 
 def _detail_slower(n):
@@ -799,15 +805,15 @@ class DynamicUpsampling(nn.Module):
         grad = tail_grad_gate(disp, fea)                # under hip_grad(): the same entries, the backward on ours
         if grad and tail_grad_route("unfold", B, fea.shape[1], h, w, self.s, fea.shape[-2:]):
             wts = Unfold3CatFunction.apply(fea, disp)
-        elif (self.s == 3 and hip_gate(fea) and h <= 65535 and B * (fea.shape[1] + 1) <= 65535 and
-                tuple(fea.shape[-2:]) == (3 * h, 3 * w)):       # cat(disp, unfold(fea)) as one pass (csrc/unfold.hip)
+        elif hip_gate(fea) and _tail_shape("unfold", B, fea.shape[1], h, w, self.s, fea.shape[-2:]):
+            # cat(disp, unfold(fea)) as one pass (csrc/unfold.hip)
             wts = ops2d.unfold3_cat(fea.contiguous(), disp.contiguous())
         else:
             wts = torch.cat((disp.unsqueeze(1), F.unfold(fea, self.s, stride=self.s).view(B, -1, h, w)), 1)
         logits = self.weight_learning(wts)
         if grad and tail_grad_gate(logits) and tail_grad_route("upsample", B, 81, h, w, self.s):
             return DynamicUpsample3Function.apply(logits, disp)
-        if self.s == 3 and hip_gate(logits) and h <= 65535:
+        if hip_gate(logits) and _tail_shape("upsample", B, 81, h, w, self.s):
             return ops2d.dynamic_upsample3(logits.contiguous(), disp.contiguous())
         wts = F.softmax(logits.view(B, s2, 9, h * w), 2)
         nb = F.unfold(self.pad(disp.unsqueeze(1)), 3).unsqueeze(1)
@@ -904,7 +910,7 @@ def warp_by_disparity(right, disp):
     B, C, H, W = right.shape
     if tail_grad_gate(right, disp) and tail_grad_route("warp", B, C, H, W):
         return WarpDisparityFunction.apply(right, disp)
-    if hip_gate(right) and H > 1 and W > 1 and H <= 65535:
+    if hip_gate(right) and _tail_shape("warp", B, C, H, W):
         return ops2d.warp_disparity(right.contiguous(), disp.contiguous())
     ys, xs = torch.meshgrid(torch.arange(H, dtype=right.dtype, device=right.device),
                             torch.arange(W, dtype=right.dtype, device=right.device), indexing="ij")

@@ -33,6 +33,18 @@ def _opt(name, t, shape=None):
     return None if t is None else _chk(name, t, shape).data_ptr()
 
 
+def _new(want, like):
+    """An optional output -> (a new tensor like `like`, its address), or (None, None) when it is not wanted."""
+    t = torch.empty_like(like) if want else None
+    return t, (t.data_ptr() if want else None)
+
+
+def _mask_words(want, B, H, W, device):
+    """The optional bit plane of a [B,H,W] mask, 64 pixels of a row per int64 word -> (tensor, address) or (None, None)."""
+    t = torch.empty((B, H, (W + 63) // 64), dtype=torch.int64, device=device) if want else None
+    return t, (t.data_ptr() if want else None)
+
+
 def _wss(w, scale, shift, wtype=_F32):
     """Packed weight (a flat library-format buffer), folded scale and shift [Cout] -> (w, scale, shift), Cout."""
     if not (w.is_cuda and w.dtype is wtype and w.is_contiguous()):
@@ -248,11 +260,10 @@ def _bn_train_backward(layout, z, gy, weight, bias, stats, relu, want_gz=True):
     if not (isinstance(stats, torch.Tensor) and stats.is_cuda and stats.dtype is torch.float64 and stats.is_contiguous() and
             stats.shape == (2 * dims[1],)):
         raise TypeError("stats must be the contiguous float64 [2 C] tensor of %s_forward, on the GPU" % layout[1])
-    gz = torch.empty_like(z) if want_gz else None
+    gz, pz = _new(want_gz, z)
     dw, db = torch.empty_like(weight), torch.empty_like(bias)
     _call("decnet_%s_backward" % layout[1], z, z.data_ptr(), gy.data_ptr(), weight.data_ptr(), bias.data_ptr(),
-          stats.data_ptr(), gz.data_ptr() if want_gz else None, dw.data_ptr(), db.data_ptr(), 1 if relu else 0,
-          ws.data_ptr(), nws, *dims)
+          stats.data_ptr(), pz, dw.data_ptr(), db.data_ptr(), 1 if relu else 0, ws.data_ptr(), nws, *dims)
     return gz, dw, db
 
 
@@ -341,7 +352,7 @@ def warp_disparity(right, disp, out=None):
     return _run("decnet_warp_disparity", (right, disp), out, (B, C, H, W), B, C, H, W)
 
 
-# ---- the full-resolution tail under hip_grad() (csrc/tail_grad.hip; the Functions are in tail_grad.py) -------------------
+# ---- the gathers of the full-resolution tail under hip_grad() (csrc/tail_grad.hip; the Functions are in tail_grad.py) ----
 def warp_disparity_backward(right, disp, gout, want_right=True, want_disp=True):
     """-> (g_right [B,C,H,W] or None, g_disp [B,H,W] or None).  A width beyond the g_right kernel's LDS plan raises
     DecnetHipError with code UNSUPPORTED (nothing launched): ask for g_disp alone then."""
@@ -350,10 +361,8 @@ def warp_disparity_backward(right, disp, gout, want_right=True, want_disp=True):
     _chk("gout", gout, (B, C, H, W))
     if not (want_right or want_disp):
         return None, None
-    gr = torch.empty_like(right) if want_right else None
-    gd = torch.empty_like(disp) if want_disp else None
-    _call("decnet_warp_disparity_backward", right, right.data_ptr(), disp.data_ptr(), gout.data_ptr(),
-          gr.data_ptr() if want_right else None, gd.data_ptr() if want_disp else None, B, C, H, W)
+    (gr, pr), (gd, pd) = _new(want_right, right), _new(want_disp, disp)
+    _call("decnet_warp_disparity_backward", right, right.data_ptr(), disp.data_ptr(), gout.data_ptr(), pr, pd, B, C, H, W)
     return gr, gd
 
 
@@ -364,14 +373,11 @@ def dynamic_upsample3_backward(logits, disp, gout, want_disp=True):
     _chk("logits", logits, (B, 81, h, w))
     _chk("gout", gout, (B, 3 * h, 3 * w))
     gl = torch.empty_like(logits)
-    gd = ws = None
-    nws = 0
-    if want_disp:
-        nws = _workspace_floats("dynamic_upsample3_backward", (B, h, w), "B %d, %d x %d")
-        gd = torch.empty_like(disp)
-        ws = torch.empty(nws, dtype=_F32, device=disp.device)         # torch allocations are 16-byte aligned
+    gd, pd = _new(want_disp, disp)
+    nws = _workspace_floats("dynamic_upsample3_backward", (B, h, w), "B %d, %d x %d") if want_disp else 0
+    ws = torch.empty(nws, dtype=_F32, device=disp.device) if want_disp else None      # (torch allocates 16-byte aligned)
     _call("decnet_dynamic_upsample3_backward", logits, logits.data_ptr(), disp.data_ptr(), gout.data_ptr(), gl.data_ptr(),
-          gd.data_ptr() if want_disp else None, ws.data_ptr() if want_disp else None, nws, B, h, w)
+          pd, ws.data_ptr() if want_disp else None, nws, B, h, w)
     return gl, gd
 
 
@@ -384,25 +390,32 @@ def fold3(g, out=None):
     return _run("decnet_fold3", (g,), out, (B, C, 3 * h, 3 * w), B, C, h, w)
 
 
+# ---- the elementwise passes under hip_grad() (csrc/detail_grad.hip; the Functions are in tail_grad.py) -------------------
 def sigmoid_blend(o, a, b, out=None):
     """a * (1 - sigmoid(o)) + sigmoid(o) * b over planes of one shape: conv2d_cat_epilogue's epilogue 1 on its own."""
     _chk("b", b, _chk("a", a, _chk("o", o).shape).shape)
     return _run("decnet_sigmoid_blend", (o, a, b), out, o.shape, o.numel())
 
 
-def sigmoid_blend_backward(o, a, b, gout, want_a=True, want_b=True):
-    """-> (g_o, g_a or None, g_b or None)."""
-    for n, t in (("a", a), ("b", b), ("gout", gout)):
-        _chk(n, t, _chk("o", o).shape)
+def _blend_backward(entry, o, a, b, grads, optional, want_a, want_b):
+    """Both blend backwards.  grads: ((name, gradient of an output of `entry`), ...); optional: all but one may be None."""
+    shape = _chk("b", b, _chk("a", a, _chk("o", o).shape).shape).shape
+    ptrs = [None if optional and t is None else _chk(n, t, shape).data_ptr() for n, t in grads]
+    if ptrs.count(None) == len(ptrs):
+        raise ValueError("%s are both None" % " and ".join(n for n, _ in grads))
     go = torch.empty_like(o)
-    ga = torch.empty_like(o) if want_a else None
-    gb = torch.empty_like(o) if want_b else None
-    _call("decnet_sigmoid_blend_backward", o, o.data_ptr(), a.data_ptr(), b.data_ptr(), gout.data_ptr(), go.data_ptr(),
-          ga.data_ptr() if want_a else None, gb.data_ptr() if want_b else None, o.numel())
+    ga = torch.empty_like(o) if want_a else None                      # (written out, not _new(): two more Python calls
+    gb = torch.empty_like(o) if want_b else None                      # per backward showed in the eager timing)
+    _call(entry, o, o.data_ptr(), a.data_ptr(), b.data_ptr(), *ptrs, go.data_ptr(), ga.data_ptr() if want_a else None,
+          gb.data_ptr() if want_b else None, o.numel())
     return go, ga, gb
 
 
-# ---- detail maps and soft masks under hip_grad() (csrc/detail_grad.hip; the Functions are in tail_grad.py) ---------------
+def sigmoid_blend_backward(o, a, b, gout, want_a=True, want_b=True):
+    """-> (g_o, g_a or None, g_b or None)."""
+    return _blend_backward("decnet_sigmoid_blend_backward", o, a, b, (("gout", gout),), False, want_a, want_b)
+
+
 def sqdiff(a, b, out=None):
     """(a - b) * (a - b) over tensors of one shape, torch's bits."""
     _chk("b", b, _chk("a", a).shape)
@@ -414,10 +427,8 @@ def sqdiff_backward(a, b, gout, want_a=True, want_b=True):
     _chk("gout", gout, _chk("b", b, _chk("a", a).shape).shape)
     if not (want_a or want_b):
         return None, None
-    ga = torch.empty_like(a) if want_a else None
-    gb = torch.empty_like(a) if want_b else None
-    _call("decnet_sqdiff_backward", a, a.data_ptr(), b.data_ptr(), gout.data_ptr(), ga.data_ptr() if want_a else None,
-          gb.data_ptr() if want_b else None, a.numel())
+    (ga, pa), (gb, pb) = _new(want_a, a), _new(want_b, a)
+    _call("decnet_sqdiff_backward", a, a.data_ptr(), b.data_ptr(), gout.data_ptr(), pa, pb, a.numel())
     return ga, gb
 
 
@@ -427,11 +438,11 @@ def detail_tail(logits, thold, want_prob=True, want_mask=True, want_bits=False):
     B, H, W = _chk("logits", logits).shape
     if not (want_prob or want_mask or want_bits):
         return None, None, None
-    prob = torch.empty_like(logits) if want_prob else None
+    prob = torch.empty_like(logits) if want_prob else None            # (written out, not _new(): as _blend_backward)
     mask = torch.empty_like(logits) if want_mask else None
-    bits = torch.empty((B, H, (W + 63) // 64), dtype=torch.int64, device=logits.device) if want_bits else None
+    bits, pb = _mask_words(want_bits, B, H, W, logits.device)
     _call("decnet_detail_tail", logits, logits.data_ptr(), float(thold), prob.data_ptr() if want_prob else None,
-          mask.data_ptr() if want_mask else None, bits.data_ptr() if want_bits else None, B, H, W)
+          mask.data_ptr() if want_mask else None, pb, B, H, W)
     return prob, mask, bits
 
 
@@ -454,18 +465,8 @@ def sigmoid_blend_soft(o, a, b):
 
 def sigmoid_blend_soft_backward(o, a, b, gout, gsoft, want_a=True, want_b=True):
     """gout, gsoft: the gradients of the two outputs, one of them may be None -> (g_o, g_a or None, g_b or None)."""
-    for n, t in (("a", a), ("b", b), ("gout", gout), ("gsoft", gsoft)):
-        if t is not None:
-            _chk(n, t, _chk("o", o).shape)
-    if gout is None and gsoft is None:
-        raise ValueError("gout and gsoft are both None")
-    go = torch.empty_like(o)
-    ga = torch.empty_like(o) if want_a else None
-    gb = torch.empty_like(o) if want_b else None
-    _call("decnet_sigmoid_blend_soft_backward", o, o.data_ptr(), a.data_ptr(), b.data_ptr(), _opt("gout", gout),
-          _opt("gsoft", gsoft), go.data_ptr(), ga.data_ptr() if want_a else None, gb.data_ptr() if want_b else None,
-          o.numel())
-    return go, ga, gb
+    grads = (("gout", gout), ("gsoft", gsoft))
+    return _blend_backward("decnet_sigmoid_blend_soft_backward", o, a, b, grads, True, want_a, want_b)
 
 
 def detail_mask_params(flat):
@@ -482,10 +483,9 @@ def detail_mask(cur3, pre3, params, thold, want_bits=False, out=None, want_logit
     if C != 3:
         raise ValueError("cur3 has %d channels, the layer takes 3" % C)
     y = torch.empty((B, H, W), dtype=_F32, device=cur3.device) if out is None else _chk("out", out, (B, H, W))
-    bits = torch.empty((B, H, (W + 63) // 64), dtype=torch.int64, device=cur3.device) if want_bits else None
-    logits = torch.empty((B, H, W), dtype=_F32, device=cur3.device) if want_logits else None
-    _call("decnet_detail_mask", cur3, cur3.data_ptr(), pre3.data_ptr(), *params, float(thold), y.data_ptr(),
-          logits.data_ptr() if want_logits else None, bits.data_ptr() if want_bits else None, B, H, W)
+    bits, pb = _mask_words(want_bits, B, H, W, cur3.device)
+    logits, pl = _new(want_logits, y)
+    _call("decnet_detail_mask", cur3, cur3.data_ptr(), pre3.data_ptr(), *params, float(thold), y.data_ptr(), pl, pb, B, H, W)
     return (y, bits, logits) if want_logits else (y, bits)
 
 

@@ -1,6 +1,6 @@
-"""Forward and backward of the full-resolution tail on HIP under ``hip_grad()``: the warp of Refinement, the head and the
-tail of DynamicUpsampling and SoftAttention's sigmoid + blend (csrc/tail_grad.hip); the squared difference and the sigmoid /
-threshold tail of GenerateSparseMask's detail map, and the blend that also hands out its soft mask (csrc/detail_grad.hip).
+"""Forward and backward of the full-resolution tail on HIP under ``hip_grad()``: the warp of Refinement and the head and
+tail of DynamicUpsampling (gathers, csrc/tail_grad.hip); SoftAttention's sigmoid + blend, with or without its soft mask, and
+the squared difference and sigmoid / threshold tail of GenerateSparseMask's detail map (passes of csrc/detail_grad.hip).
 
 Each Function runs the entry that inference runs (``decnet_warp_disparity``, ``decnet_unfold3_cat``,
 ``decnet_dynamic_upsample3``; the blend is the statement sequence of ``decnet_conv2d_cat_epilogue``'s epilogue 1), so a
@@ -93,6 +93,17 @@ class DynamicUpsample3Function(Function):
         return (gl if want_l else None), gd
 
 
+def _blend_backward(ctx, backward, *grads):
+    """Both blend Functions' backward; `backward`: the ops2d wrapper of the Function's own entry (a grad may be None)."""
+    o, a, b = ctx.saved_tensors
+    want_o, want_a, want_b = ctx.needs_input_grad
+    if all(g is None for g in grads) or not (want_o or want_a or want_b):
+        return None, None, None
+    want_a, want_b = want_a and grads[0] is not None, want_b and grads[0] is not None   # (the soft mask does not read them)
+    go, ga, gb = backward(o, a, b, *[None if g is None else g.contiguous() for g in grads], want_a, want_b)
+    return (go if want_o else None), ga, gb
+
+
 class SigmoidBlendFunction(Function):
     """apply(o, a, b) -> a * (1 - sigmoid(o)) + sigmoid(o) * b, planes of one shape (decnet_sigmoid_blend)."""
 
@@ -105,12 +116,7 @@ class SigmoidBlendFunction(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, gout):
-        o, a, b = ctx.saved_tensors
-        want_o, want_a, want_b = ctx.needs_input_grad
-        if not (want_o or want_a or want_b):
-            return None, None, None
-        go, ga, gb = ops2d.sigmoid_blend_backward(o, a, b, gout.contiguous(), want_a, want_b)
-        return (go if want_o else None), ga, gb
+        return _blend_backward(ctx, ops2d.sigmoid_blend_backward, gout)
 
 
 class SquaredDiffFunction(Function):
@@ -167,11 +173,4 @@ class SigmoidBlendSoftFunction(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, gout, gsoft):
-        o, a, b = ctx.saved_tensors
-        want_o, want_a, want_b = ctx.needs_input_grad
-        if (gout is None and gsoft is None) or not (want_o or want_a or want_b):
-            return None, None, None
-        want_a, want_b = want_a and gout is not None, want_b and gout is not None       # (the soft mask does not read them)
-        go, ga, gb = ops2d.sigmoid_blend_soft_backward(o, a, b, None if gout is None else gout.contiguous(),
-                                                       None if gsoft is None else gsoft.contiguous(), want_a, want_b)
-        return (go if want_o else None), ga, gb
+        return _blend_backward(ctx, ops2d.sigmoid_blend_soft_backward, gout, gsoft)

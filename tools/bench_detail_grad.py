@@ -9,8 +9,10 @@ Per level and BatchNorm mode, forward + backward of (prob * r).sum():
   torch  the same module under hip_grad() (the units on the same routes) with the tail in torch ops: sigmoid(gen(cur, pre))
          and the reference's threshold statements (clone, two masked fills, under no_grad) -- the yardstick
 each eager and as one GraphedStep replay.  SoftAttention(C + 4, 8).fuse(want_soft=True) against the same units followed by
-torch's sigmoid and blend, in the same way.  The six kernels alone at the first level: `--calls` calls per graph replay,
-time against the algorithmic bytes at 8 TB/s.  One process, alternating blocks, `--repeats` blocks of `--calls` calls after
+torch's sigmoid and blend, in the same way.  The entries of csrc/detail_grad.hip and decnet_detail_mask alone at the first
+level (`kernels`; `--kernels-only` stops after them): `--calls` calls per graph replay, time against the algorithmic bytes
+at 8 TB/s, and `alone_us_per_call`, the same calls eager -- the ops2d wrapper and the launch, bound by the host where the
+kernel is shorter than they are.  One process, alternating blocks, `--repeats` blocks of `--calls` calls after
 a warm-up; medians.  model._detail_slower, the exclusion these numbers decide, is switched off for the run: the hip leg is
 the Functions at every level."""
 import argparse
@@ -135,6 +137,8 @@ def kernel_rows(dev, B, calls, repeats):
     a3, b3, g3 = rn(B, 3, H, W), rn(B, 3, H, W), rn(B, 3, H, W)
     z, o, a, b, g1, g2 = (rn(B, H, W) for _ in range(6))
     n3, n1 = float(a3.numel()), float(z.numel())
+    params = ops2d.detail_mask_params([0.01 * ((i * 37) % 11 - 5) for i in range(81)] + [1.0] * 3 + [0.0] * 3 + [0.3] * 3 +
+                                      [1.0, -0.5])
     kernels = {}
     with torch.no_grad():
         for name, fn, nbytes in (
@@ -143,16 +147,23 @@ def kernel_rows(dev, B, calls, repeats):
                 ("detail_tail", lambda: ops2d.detail_tail(z, THOLD, True, True, True), (12.0 + 1.0 / 8) * n1),
                 ("detail_tail_backward", lambda: ops2d.detail_tail_backward(z, g1), 12.0 * n1),
                 ("sigmoid_blend_soft", lambda: ops2d.sigmoid_blend_soft(o, a, b), 20.0 * n1),
-                ("sigmoid_blend_soft_backward", lambda: ops2d.sigmoid_blend_soft_backward(o, a, b, g1, g2), 32.0 * n1)):
-            fn()
-            torch.cuda.synchronize()
+                ("sigmoid_blend_soft_backward", lambda: ops2d.sigmoid_blend_soft_backward(o, a, b, g1, g2), 32.0 * n1),
+                ("sigmoid_blend_soft_backward_gsoft_only",
+                 lambda: ops2d.sigmoid_blend_soft_backward(o, a, b, None, g2, False, False), 12.0 * n1),
+                ("sigmoid_blend", lambda: ops2d.sigmoid_blend(o, a, b), 16.0 * n1),
+                ("sigmoid_blend_backward", lambda: ops2d.sigmoid_blend_backward(o, a, b, g1), 28.0 * n1),
+                ("detail_mask", lambda: ops2d.detail_mask(a3, b3, params, THOLD, True), (8.0 * n3 + (4.0 + 1.0 / 8) * n1))):
+            for _ in range(10):
+                fn()
+            alone = stats([timed(fn, calls) * 1e3 for _ in range(repeats)])
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
                 for _ in range(calls):
                     fn()
             graph.replay()
             us = stats([timed(graph.replay, 1) / calls * 1e3 for _ in range(repeats)])
-            kernels[name] = {"us_per_call": us, "bytes": nbytes, "share_of_hbm_roof_at_median": nbytes / HBM * 1e6 / us["median"]}
+            kernels[name] = {"us_per_call": us, "alone_us_per_call": alone, "bytes": nbytes,
+                             "share_of_hbm_roof_at_median": nbytes / HBM * 1e6 / us["median"]}
             print(json.dumps({name: kernels[name]}), flush=True)
             del graph
     return kernels
@@ -165,6 +176,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--batch", type=int, default=4)
+    ap.add_argument("--kernels-only", action="store_true")
     a = ap.parse_args()
     import torch
     import decnet_amd
@@ -175,9 +187,10 @@ def main():
     model._detail_slower = lambda n: False
     report = {"device": torch.cuda.get_device_name(0), "version": decnet_amd.version(), "batch": a.batch,
               "levels_H_W_C": [list(v) for v in LEVELS], "calls": a.calls, "repeats": a.repeats, "warmup": a.warmup,
-              "hbm_B_per_s": HBM, "kernels": kernel_rows(dev, a.batch, a.calls, a.repeats),
-              "detail_ms_forward_backward": detail_rows(dev, a.batch, a.calls, a.repeats, a.warmup),
-              "fuse_ms_forward_backward": fuse_rows(dev, a.batch, a.calls, a.repeats, a.warmup)}
+              "hbm_B_per_s": HBM, "kernels": kernel_rows(dev, a.batch, a.calls, a.repeats)}
+    if not a.kernels_only:
+        report["detail_ms_forward_backward"] = detail_rows(dev, a.batch, a.calls, a.repeats, a.warmup)
+        report["fuse_ms_forward_backward"] = fuse_rows(dev, a.batch, a.calls, a.repeats, a.warmup)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(report, f, indent=1, sort_keys=True)

@@ -1,13 +1,16 @@
 #!/usr/bin/env python
 """Two builds of one csrc/*.hip, kernel for kernel: the register / LDS / scratch metadata and the instruction stream.
 
-    python tools/compare_kernels.py PARENT/decnet_amd/csrc/x.hip decnet_amd/csrc/x.hip [OUT.json]
+    python tools/compare_kernels.py PARENT/decnet_amd/csrc/x.hip decnet_amd/csrc/x.hip [OUT.json [RENAMES.json]]
 
 Compiles both with the flags of decnet_amd/build.py plus `--cuda-device-only -S` (no GPU needed), drops comments, `.loc`,
 `.file`, `.ident` and the other directives, and matches the kernels by demangled name and template arguments (without the
 parameter list and the unnamed namespace, so a parameter type that moved to a header does not unmatch a kernel).  Prints
 one line per kernel that differs and a count; OUT.json gets every kernel: metadata of both, waves per SIMD of both (512
 unified registers per lane and SIMD on gfx950, allocated in eights, at most 8 waves), instruction counts, `same_code`.
+Either side may be several files joined by commas (kernels that moved between files): their kernels are taken together.
+RENAMES.json, {tree kernel: parent kernel}, pairs kernels whose names changed (several tree kernels may name one parent
+kernel); such a pair is compared like any other and reported as "parent kernel -> tree kernel".
 Exit status 1 when a kernel is unmatched."""
 import json
 import os
@@ -55,8 +58,25 @@ def waves(m):
     return min(8, 512 // (-(-max(m["vgpr_count"], 1) // 8) * 8))
 
 
-def main(parent, tree, out=None):
-    a, b = kernels(assembly(parent)), kernels(assembly(tree))
+def all_kernels(srcs):
+    out = {}
+    for src in srcs.split(","):
+        ks = kernels(assembly(src))
+        assert not set(ks) & set(out), sorted(set(ks) & set(out))
+        out.update(ks)
+    return out
+
+
+def main(parent, tree, out=None, renames=None):
+    a, b = all_kernels(parent), all_kernels(tree)
+    if renames:
+        with open(renames) as f:
+            renames = json.load(f)
+        assert not set(renames) & set(a) and not set(renames.values()) & set(b), "a renamed kernel kept its name"
+        a.update({"%s -> %s" % (old, new): a[old] for new, old in renames.items()})
+        b.update({"%s -> %s" % (old, new): b.pop(new) for new, old in renames.items()})
+        for old in set(renames.values()):
+            del a[old]
     doc, differ = {}, 0
     for k in sorted(set(a) & set(b)):
         same = a[k]["code"] == b[k]["code"]
@@ -76,4 +96,4 @@ def main(parent, tree, out=None):
 
 
 if __name__ == "__main__":
-    sys.exit(main(*sys.argv[1:4]))
+    sys.exit(main(*sys.argv[1:5]))
